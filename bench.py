@@ -4,8 +4,8 @@
 Metric (BASELINE.json): input MB/s encode+decode, 100 MB blocks, -3 and -5;
 bit-exact vs CPU.  Default workload (configs[1]): a synthetic 1 GB Illumina
 150 bp FASTQ with 8-level binned qualities and Illumina names at -3, split
-into 100 MB blocks by the reference's record rule (fqzcomp5.c:471-477).  The
-default run adds configs[2] as the `level5` item: a synthetic 4 GB NovaSeq
+into 100 MB blocks by the reference's record rule (fqzcomp5.c:471-477).  A
+`--full` run adds configs[2] as the `level5` item: a synthetic 4 GB NovaSeq
 FASTQ per GPU at -5.  One step is one pass of the hot path over the whole
 workload, the records resident in HBM (names, bases, qualities; lengths on
 the host):
@@ -23,8 +23,8 @@ between them).  Reported per workload:
     enc_MBps, dec_MBps   the same bytes over t_enc and t_dec alone
     section_MBps         the name+seq+qual section bytes over t_enc + t_dec
 The blocks equal the reference CLI's blocks byte for byte (checked against
-the CPU baseline's file when it runs); the FASTQ parse and the file write
-are outside the timed region (the records are already in HBM).
+the CPU baseline's file when it runs, `--full`); the FASTQ parse and the
+file write are outside the timed region (the records are already in HBM).
 
 Methods: the level presets' name, sequence and quality masks
 (fqzcomp5.c:4886-4932, :2750-2793), every one coded by this build.
@@ -36,11 +36,20 @@ blocks of all ranks in rank order (the only collective: an all-gather of the
 candidate sizes, sections.exchange_sizes).  `--scaling strong` shards the
 blocks of one fixed file contiguously over the ranks.
 
-Also reported: the roofline of the dominant kernel from live HIP events on
-the library's stream; the reference CLI (oracle/_ref, compiled from the
-reference sources, as shipped and with its x86 SIMD dispatch) on the host
-cores over the same FASTQ text, its blocks compared with the GPU's; and the
-reference CLI relinked on this library (the drop-in) on the same file.
+A plain run (`--gpus 1 --steps N --warmup W`) sets up the default workload,
+warms up, times the N steps and prints the result line: the figures above,
+`ms_per_step` (one timed step, encode + decode), the round trip check of the
+last step and the roofline of the dominant kernel from the timed steps' own
+HIP events on the library's stream.  `--dump-outputs DIR` writes what the
+last timed step computed as DIR/<name>.npy (dump_outputs); the inputs are
+seeded, so the files of two runs with the same arguments are equal.
+
+`--full` adds everything else to the line: the reference CLI (oracle/_ref,
+compiled from the reference sources, as shipped and with its x86 SIMD
+dispatch) on the host cores over the same FASTQ text, its blocks compared
+with the GPU's; the `level5` and `level5_illumina` items; the block checksum
+item; and the reference CLI relinked on this library (the drop-in) on the
+same file.  Each has its --no-* option.
 """
 from __future__ import annotations
 
@@ -73,6 +82,8 @@ GAP_S = float(os.environ.get("FQZ5_BENCH_GAP_S", "0") or 0)
 STEP_TRACE = bool(os.environ.get("FQZ5_STEP_TRACE"))   # per-phase decode times on stderr
 BLK = 100_000_000        # -3 / -5 block size (fqzcomp5.c:4896,4904)
 HBM_PEAK_GBS = 8000.0    # MI355X_MICROARCH.md: 8 TB/s spec
+DUMP_SAMPLE = 6_000_000  # --dump-outputs: elements of a sampled byte array (float32: 24 MB)
+DUMP_SEED = 20240531     # and the seed of the sample's positions
 # fqz5_profile_read_all's kernels, in its order (include/fqz5_mi355x.h); each
 # launch timed by HIP events around it on its own stream.  k_enc_replay is
 # the emitting pass (rocprof: k_enc_replay<true>), k_enc_replay0 the
@@ -230,14 +241,55 @@ def t1_pin(gpu_blocks, golden: str, fastq_md5=None):
     return out
 
 
+def dump_outputs(d, run, res, meth_all, rank, world):
+    """What the last timed step computed, as float .npy files under `d` (at
+    most 64 MB over all ranks; rank 0's files are `<name>.npy`, rank r's
+    `rank<r>_<name>.npy`).  The encode's results: every block's size, every
+    section's chosen method and coded size, the byte sum of every block, and
+    the assembled blocks' bytes.  The decode's: the byte sum of every decoded
+    section and the decoded bytes.  Byte arrays above DUMP_SAMPLE / world
+    elements are written as a fixed sample (sorted positions drawn with
+    DUMP_SEED over the array's length)."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    pre = "" if rank == 0 else f"rank{rank}_"
+
+    def save(name, a):
+        np.save(os.path.join(d, pre + name + ".npy"), a)
+
+    def sample(buf, n):
+        k = DUMP_SAMPLE // world
+        if n > k:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, k))
+            buf = buf[torch.from_numpy(idx).to(buf.device)]
+        else:
+            buf = buf[:n]
+        return buf.cpu().numpy().astype(np.float32)
+
+    def sums(buf, bounds):
+        return np.asarray([int(buf[s:e].sum(dtype=torch.int64)) for s, e in bounds], np.float64)
+
+    off = [int(x) for x in run.blk_off]
+    save("block_sizes", np.diff(np.asarray(off, np.float64)))
+    save("section_methods", np.asarray([int(m) for m in meth_all], np.float64))
+    save("section_sizes", np.asarray([int(r.clen) for r in res], np.float64))
+    save("block_byte_sums", sums(run.blk_buf, zip(off[:-1], off[1:])))
+    save("blocks", sample(run.blk_buf, off[-1]))
+    save("decoded_section_byte_sums",
+         sums(run.dec_buf, [(do, do + e - s) for (_, s, e, _, _), do in zip(run.spans, run.dec)]))
+    save("decoded", sample(run.dec_buf, run.in_bytes))
+
+
 def measure(level, kind, gb, steps, warmup, cpu, cpu_threads, world, rank, local, dist,
-            scaling="weak", pmc_tag="", dropin=False, t1_blocks=0, gpu_only=False, pin=None):
+            scaling="weak", pmc_tag="", dropin=False, t1_blocks=0, gpu_only=False, pin=None,
+            dump=None):
     """One workload: warmup + `steps` timed steps (barrier + synchronize on
     both sides, max over ranks) and the result fields of its JSON line.  The
     decode places each adaptive-model chain (fqz quality, sequence model) on
     a host core or the GPU by its measured cost (fqz5_set_host_decode(2), the
     library's default).  gpu_only: then time the decode again with every
-    chain on the GPU (fqz5_set_host_decode(0)), reported apart."""
+    chain on the GPU (fqz5_set_host_decode(0)), reported apart.  dump: a
+    directory for the last timed step's outputs (dump_outputs)."""
     import torch
     from fqzcomp5_amd import lib, sections as S, synth
 
@@ -335,6 +387,8 @@ def measure(level, kind, gb, steps, warmup, cpu, cpu_threads, world, rank, local
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
     dt, t_enc, t_dec = (float(x) for x in tm.tolist())
     fq_all, sec_all = (float(x) for x in tot.tolist())
+    if dump:
+        dump_outputs(dump, run, res, meth_all[off:off + len(res)], rank, world)   # this rank's
 
     # ---- correctness: every decoded section equals its input -------------
     ok = all(r.status == 0 for r in res) and all(r.status == 0 for r in dres)
@@ -627,7 +681,7 @@ def dropin_item(fastq: str, level: int, threads: int, timeout: int = 600):
         return {"error": str(e)[-300:]}
 
 
-def relaunch(n: int) -> None:
+def relaunch(n: int, argv) -> None:
     """Start `n` ranks of this script under torch.distributed.run (one
     process per GPU) and exit with its status.  Runs before anything has
     touched the GPU."""
@@ -637,12 +691,12 @@ def relaunch(n: int) -> None:
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
            f"--nproc-per-node={n}", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.abspath(__file__)] + sys.argv[1:]
+           os.path.abspath(__file__)] + list(argv)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     raise SystemExit(subprocess.call(cmd, env=env))
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -658,10 +712,18 @@ def main():
                     help="host threads of the CPU baseline (0: all this process may use)")
     ap.add_argument("--no-crc", action="store_true", help="skip the block-checksum item")
     ap.add_argument("--no-dropin", action="store_true", help="skip the drop-in CLI item")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline workload also run the CPU baseline, the level5 "
+                         "and level5_illumina items, the block-checksum item and the drop-in "
+                         "CLI item (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the headline workload's last timed step computed as "
+                         "DIR/<name>.npy (dump_outputs)")
+    args = ap.parse_args(argv)
+    cpu = args.full and not args.no_cpu
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        relaunch(args.gpus)
+        relaunch(args.gpus, sys.argv[1:] if argv is None else argv)
 
     import torch
     import torch.distributed as dist
@@ -692,10 +754,11 @@ def main():
         raise SystemExit("no GPU: " + lib.last_error())
     threads = args.cpu_threads or host_threads()
 
-    m = measure(args.level, args.kind, args.gb, args.steps, args.warmup, not args.no_cpu,
+    m = measure(args.level, args.kind, args.gb, args.steps, args.warmup, cpu,
                 threads, world, rank, local, dist, scaling=args.scaling,
                 pmc_tag="" if args.level == 3 else f"_l{args.level}",
-                dropin=not args.no_dropin and args.level == 3)
+                dropin=args.full and not args.no_dropin and args.level == 3,
+                dump=args.dump_outputs)
     out = {"metric": "input MB/s encode+decode, 100MB blocks, -3 and -5; bit-exact vs CPU",
            "value": m["value"], "unit": "MB/s", "n_gpus": world, "steps": args.steps,
            "warmup": args.warmup, "ms_per_step": m["ms_per_step"], "higher_is_better": True,
@@ -711,9 +774,9 @@ def main():
     # The metric covers -3 and -5: the default run adds configs[2] (-5,
     # 4 GB NovaSeq per GPU) as its own item with the same timing rules;
     # `value` stays configs[1] (-3).
-    if not args.no_level5 and args.level == 3:
+    if args.full and not args.no_level5 and args.level == 3:
         out["level5"] = measure(5, "novaseq", 4.0 if args.scaling == "weak" else 4.0 * world,
-                                args.steps, args.warmup, not args.no_cpu, threads, world,
+                                args.steps, args.warmup, cpu, threads, world,
                                 rank, local, dist, scaling=args.scaling, pmc_tag="_l5",
                                 t1_blocks=4, pin="l5_novaseq.json")
         # -5 on configs[1]'s data: the random-walk binned Illumina qualities,
@@ -723,10 +786,10 @@ def main():
         # decode: fewer steps
         out["level5_illumina"] = measure(5, "illumina", args.gb if args.scaling == "weak"
                                          else args.gb * world, min(args.steps, 2),
-                                         min(args.warmup, 1), not args.no_cpu, threads, world,
+                                         min(args.warmup, 1), cpu, threads, world,
                                          rank, local, dist, scaling=args.scaling,
                                          pmc_tag="_l5i", t1_blocks=4, gpu_only=True)
-    if rank == 0 and world == 1 and not args.no_crc:
+    if rank == 0 and world == 1 and args.full and not args.no_crc:
         out["crc32"] = crc_item(lib, torch)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -16,7 +16,7 @@ B3="--no-cpu --no-level5 --no-crc --no-dropin"
 B5="--no-cpu --no-crc --no-dropin --level 5 --kind novaseq --gb 4"
 B5I="--no-cpu --no-crc --no-dropin --no-level5 --level 5 --kind illumina"
 if [ "$PHASE" != b ]; then
-timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.log
+timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.log
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt3 -o kt -- \
     python3 bench.py $B3 --steps 5 --warmup 1 > $OUT/kt3.log 2>&1
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt5 -o kt -- \
