@@ -13,6 +13,11 @@
 // one wave); the section bytes are gathered one wave per record at the
 // scanned offsets.  FASTQ that is not 4-line (multi-line records) is refused
 // with an error, never parsed on the host.
+//
+// fqz5_fastq_format_range writes the text of a range of a decoded block's
+// records (record ranges read through the file's block index): the records'
+// sizes, their output offsets and the sequence offsets are computed and
+// scanned on the device, and the host sees the totals only.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -461,16 +466,19 @@ __global__ void k_fq_flags(const fqz5_fastq_rec *recs, uint64_t a, uint64_t n, c
 
 // output_fastq (fqzcomp5.c:3441-3480): '@' name '\n' seq '\n' '+' [name] '\n'
 // qual+33 '\n'; without qualities output_fasta (:3503-3517): '>' name '\n'
-// seq '\n'.  One wave per record.
+// seq '\n'.  One wave per record: wave j writes record base + j of the block
+// (zpos, soff and lens are the block's) at ooff[j].
 __global__ void k_fq_format(const uint8_t *names, const uint64_t *zpos, const uint8_t *seq,
                             const uint8_t *qual, const uint64_t *soff, const uint32_t *lens,
-                            const uint64_t *ooff, uint64_t n, int plus_name, uint8_t *out) {
-    const uint64_t k = (uint64_t(blockIdx.x) * blockDim.x + threadIdx.x) / 64;
+                            const uint64_t *ooff, uint64_t base, uint64_t n, int plus_name,
+                            uint8_t *out) {
+    const uint64_t j = (uint64_t(blockIdx.x) * blockDim.x + threadIdx.x) / 64;
     const uint32_t lane = threadIdx.x & 63;
-    if (k >= n) return;
+    if (j >= n) return;
+    const uint64_t k = base + j;
     const uint64_t ns = k ? zpos[k - 1] + 1 : 0;
     const uint32_t nl = uint32_t(zpos[k] - ns), L = lens[k];
-    uint8_t *o = out + ooff[k];
+    uint8_t *o = out + ooff[j];
     if (lane == 0) o[0] = qual ? '@' : '>';
     for (uint32_t i = lane; i < nl; i += 64) o[1 + i] = names[ns + i];
     uint64_t w = 1 + nl;
@@ -497,6 +505,37 @@ __global__ void k_fq_format(const uint8_t *names, const uint64_t *zpos, const ui
     for (uint32_t i = lane; i < L; i += 64) o[w + i] = uint8_t(qp[i] + 33);
     w += L;
     if (lane == 0) o[w] = '\n';
+}
+
+// Text sizes of records base .. base + n of a block (k_fq_format's bytes per
+// record) from the name terminators and the lengths; entry n is 0, so an
+// exclusive scan over n + 1 entries ends with the total.  odd (pairs): the
+// even records' sizes into size (0 for an odd record), the odd ones' into odd.
+__global__ void k_fq_sizes(const uint64_t *zpos, const uint32_t *lens, uint64_t base, uint64_t n,
+                           int fastq, int plus_name, uint64_t *size, uint64_t *odd) {
+    const uint64_t j = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (j > n) return;
+    uint64_t sz = 0;
+    const uint64_t k = base + j;
+    if (j < n) {
+        const uint64_t nl = zpos[k] - (k ? zpos[k - 1] + 1 : 0), L = lens[k];
+        sz = fastq ? 1 + nl + 1 + L + 2 + (plus_name ? nl : 0) + 1 + L + 1 : 1 + nl + 1 + L + 1;
+    }
+    if (odd) {
+        size[j] = (k & 1) ? 0 : sz;
+        odd[j] = (k & 1) ? sz : 0;
+    } else {
+        size[j] = sz;
+    }
+}
+
+// pairs: the scanned even offsets (oe) and odd offsets (oo) into one offset
+// per record, the odd records' text after all the even ones' (oe[n])
+__global__ void k_fq_pair_offsets(const uint64_t *oe, const uint64_t *oo, uint64_t base, uint64_t n,
+                                  uint64_t *ooff) {
+    const uint64_t j = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    ooff[j] = ((base + j) & 1) ? oe[n] + oo[j] : oe[j];
 }
 
 dim3 grid_for(uint64_t n, uint32_t per) { return dim3(uint32_t((n + per - 1) / per ? (n + per - 1) / per : 1)); }
@@ -983,7 +1022,7 @@ static int format_impl(const uint8_t *d_names, uint64_t name_len, const uint8_t 
         const uint32_t *d_l = g.upload(h_len, nrec);
         if (nrec)
             hipLaunchKernelGGL(k_fq_format, grid_for(nrec * 64, 256), dim3(256), 0, g.stream, d_names, z,
-                               d_seq, d_qual, d_so, d_l, d_oo, nrec, plus_name, d_out);
+                               d_seq, d_qual, d_so, d_l, d_oo, uint64_t(0), nrec, plus_name, d_out);
         FQZ5_HIP(hipGetLastError());
         g.reset();
         return 0;
@@ -1008,6 +1047,76 @@ int fqz5_fastq_format_pairs(const uint8_t *d_names, uint64_t name_len, const uin
     uint64_t dummy = 0;
     return format_impl(d_names, name_len, d_seq, d_qual, h_len, nrec, plus_name, d_out, out_cap,
                        out_len, r1_len ? r1_len : &dummy);
+}
+
+// Records [rec_first, rec_first + rec_count) of a block, laid out on the
+// device: the sizes of the slice's records (k_fq_sizes), their exclusive
+// scans for the output offsets (pairs: the even records', then the odd ones'
+// placed after the even total) and the scan of the lengths before the slice
+// end for the sequence offsets.  The host sees the totals only.
+int fqz5_fastq_format_range(const uint8_t *d_names, uint64_t name_len, const uint8_t *d_seq,
+                            const uint8_t *d_qual, const uint32_t *h_len, uint64_t nrec,
+                            uint64_t rec_first, uint64_t rec_count, int plus_name, int pairs,
+                            uint8_t *d_out, uint64_t out_cap, uint64_t *out_len,
+                            uint64_t *r1_len) {
+    GpuCtx *gp = nullptr;
+    try {
+        if (rec_first > nrec || rec_count > nrec - rec_first)
+            throw GpuError("fastq_format_range: the slice runs past the block's records");
+        *out_len = 0;
+        if (r1_len) *r1_len = 0;
+        if (!rec_count) return 0;
+        const uint64_t end = rec_first + rec_count, n = rec_count;
+        if (end >= (1ull << 31)) throw GpuError("fastq_format_range: block too large");
+        GpuCtx &g = gpu();
+        gp = &g;
+        uint64_t nz = 0;
+        uint64_t *z = find_delims(g, d_names, name_len, 0, &nz);
+        if (nz < end) throw GpuError("fastq_format_range: fewer names than records");
+        const uint32_t *d_l = g.upload(h_len, end);
+        // soff: bases before each record, over every record before the slice end
+        uint64_t *l64 = g.arena.alloc_n<uint64_t>(size_t(end));
+        uint64_t *soff = g.arena.alloc_n<uint64_t>(size_t(end));
+        hipLaunchKernelGGL(k_widen, grid_for(end, 256), dim3(256), 0, g.stream, d_l, l64, end);
+        FQZ5_HIP(hipGetLastError());
+        excl_sum(g, l64, soff, end);
+        // ooff: text bytes before each record of the slice; entry n the total
+        uint64_t *sz = g.arena.alloc_n<uint64_t>(size_t(n) + 1);
+        uint64_t *ooff = g.arena.alloc_n<uint64_t>(size_t(n) + 1);
+        uint64_t *szo = pairs ? g.arena.alloc_n<uint64_t>(size_t(n) + 1) : nullptr;
+        hipLaunchKernelGGL(k_fq_sizes, grid_for(n + 1, 256), dim3(256), 0, g.stream, z, d_l, rec_first, n,
+                           d_qual ? 1 : 0, plus_name, sz, szo);
+        FQZ5_HIP(hipGetLastError());
+        uint64_t tot[2] = {0, 0};
+        if (pairs) {
+            uint64_t *oe = g.arena.alloc_n<uint64_t>(size_t(n) + 1);
+            uint64_t *oo = g.arena.alloc_n<uint64_t>(size_t(n) + 1);
+            excl_sum(g, sz, oe, n + 1);
+            excl_sum(g, szo, oo, n + 1);
+            hipLaunchKernelGGL(k_fq_pair_offsets, grid_for(n, 256), dim3(256), 0, g.stream, oe, oo, rec_first,
+                               n, ooff);
+            FQZ5_HIP(hipGetLastError());
+            g.download(&tot[0], oe + n, 1);
+            g.download(&tot[1], oo + n, 1);
+        } else {
+            excl_sum(g, sz, ooff, n + 1);
+            g.download(&tot[0], ooff + n, 1);
+        }
+        g.sync();
+        *out_len = tot[0] + tot[1];
+        if (r1_len) *r1_len = pairs ? tot[0] : *out_len;
+        if (!d_out) { g.reset(); return 0; }
+        if (*out_len > out_cap) throw GpuError("fastq_format_range: output larger than out_cap");
+        hipLaunchKernelGGL(k_fq_format, grid_for(n * 64, 256), dim3(256), 0, g.stream, d_names, z, d_seq,
+                           d_qual, soff, d_l, ooff, rec_first, n, plus_name, d_out);
+        FQZ5_HIP(hipGetLastError());
+        g.reset();
+        return 0;
+    } catch (const std::exception &e) {
+        fqz5_set_error(e.what());
+        try { if (gp) gp->reset(); } catch (...) {}
+        return -1;
+    }
 }
 
 }  // extern "C"

@@ -12,12 +12,24 @@ fqzcomp5 writes, produced and read by this library alone.
     compress_paired_bytes / decompress_paired_bytes: the same for R1/R2
     pairs (encode_interleaved / decode_deinterleaved, fqzcomp5.c:3211,
     :4049): records interleaved R1, R2, R1, ... with READ2 on the R2 ones.
+    extract_file(src, dst, first, count[, dst2=]) / extract_bytes: records
+                                     [first, first + count) (dst2: pairs)
+                                     through the block index: read_index ->
+                                     cover -> only the covering blocks read,
+                                     checked against the index and decoded
+                                     -> fqz5_fastq_format_range (the text of
+                                     the wanted records, laid out on the
+                                     device); with_qual=False: no quality
+                                     section decoded, FASTA text
 
 File layout (fqzcomp5.c:2563-2630, :2959-2969): "FQZ5\\1\\1\\0\\0", u64 index
 offset, the blocks, then "FQZ5IDX\\0", u32 nblocks and per block {u64 file
-offset, u32 bases, u32 records}.  Encoding follows a single-threaded (-t1)
-reference run: the codec trial runs over the blocks in file order, so the
-file equals the reference CLI's `-<level> -t1` output byte for byte.
+offset, u32 bases, u32 records}.  The reference reads the index only for
+--inspect; here read_index / cover / extract_file use it for record ranges
+(files without one are walked by their block size fields).  Encoding follows
+a single-threaded (-t1) reference run: the codec trial runs over the blocks
+in file order, so the file equals the reference CLI's `-<level> -t1` output
+byte for byte.
 
 Scope: 4-line FASTQ, wrapped (multi-line) FASTQ as kseq_read reads it
 (kseq.h:194-216; fastq.hip's record chain) and FASTA with any line wrapping
@@ -79,12 +91,18 @@ def _load():
         so.fqz5_fastq_format_pairs.restype = C.c_int
         so.fqz5_fastq_format_pairs.argtypes = so.fqz5_fastq_format.argtypes + [
             C.POINTER(C.c_uint64)]
+        so.fqz5_fastq_format_range.restype = C.c_int
+        so.fqz5_fastq_format_range.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
+                                               C.c_int, C.c_int, C.c_void_p, C.c_uint64,
+                                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         _bound = True
     return so
 
 
 # $FQZ5_FILE_TRACE: host wall time per stage of compress_file /
 # decompress_file on stderr (read, upload, parse, gather, codec, assemble,
+# download, write; extract_file: index, read, upload, decode, format,
 # download, write); the stages end with what the library synchronises
 _TRACE = {}
 
@@ -1313,14 +1331,26 @@ def check_blocks(data, ranges=None) -> list[dict]:
     return [block_fields(data, s, e, v) for s, e in ranges]
 
 
-def _decode(data, buf, plus_name: bool, device: str, pairs: bool = False, ranges=None):
+def _decode(data, buf, plus_name: bool, device: str, pairs: bool = False, ranges=None,
+            slices=None, with_qual: bool = True):
     """Blocks of a .fqz5 (host view `data`, device copy `buf`; `ranges` the
     block byte ranges within them, all blocks of the file by default) ->
     the FASTQ text of every block in one device buffer; pairs: (the R1
     text, the R2 text) of output_fastq_deinterleaved (fqzcomp5.c:3612-3676),
-    even records of every block to R1 and odd ones to R2."""
+    even records of every block to R1 and odd ones to R2.
+
+    slices: per block (rec_first, rec_count), the records whose text is
+    wanted (extract_file): every block is still decoded whole, and its text
+    is laid out by fqz5_fastq_format_range for those records only.
+    with_qual False: the quality sections are not decoded and the text is
+    output_fasta's ('>' name, sequence)."""
+    import contextlib
     import torch
     so = _load()
+    # (the range path's $FQZ5_FILE_TRACE stages; whole-file callers time the call)
+    st_dec = _stage("decode") if slices is not None else contextlib.nullcontext()
+    st_fmt = _stage("format") if slices is not None else contextlib.nullcontext()
+    st_dec.__enter__()
     if ranges is None:
         ranges = _blocks_of(data)
     version = getattr(ranges, "version", V11)
@@ -1362,7 +1392,7 @@ def _decode(data, buf, plus_name: bool, device: str, pairs: bool = False, ranges
                               v.name_ulen, 0, S.SEC_NAME, rl, None, len(ln), None))
         secs.append(S.Section(base + s + v.seq_off, out_d.data_ptr() + po[1], v.seq_size,
                               v.seq_ulen, 0, S.SEC_SEQ, rl, None, len(ln), None))
-        if not fa:
+        if not fa and with_qual:
             secs.append(S.Section(base + s + v.qual_off, out_d.data_ptr() + po[2], v.qual_size,
                                   v.qual_ulen, 0, S.SEC_QUAL, rl, None, len(ln),
                                   out_d.data_ptr() + po[1]))
@@ -1371,14 +1401,20 @@ def _decode(data, buf, plus_name: bool, device: str, pairs: bool = False, ranges
     res = S.decode(secs)
     if any(r.status != 0 for r in res):
         raise _lib.NativeError("section decoding failed: " + _lib.last_error())
+    st_dec.__exit__(None, None, None)
+    st_fmt.__enter__()
     # the text of every block, one after the other in one device buffer
     fmt = so.fqz5_fastq_format_pairs if pairs else so.fqz5_fastq_format
+    if slices is not None:
+        def fmt(*a):                      # a[6]: the block's (rec_first, rec_count)
+            return so.fqz5_fastq_format_range(*a[:6], *a[6], int(plus_name), int(pairs), *a[7:10],
+                                              a[10] if pairs else None)
     args, sizes, r1 = [], [], []
-    for v, ln, po, fa in zip(views, lens, places, fasta):
+    for j, (v, ln, po, fa) in enumerate(zip(views, lens, places, fasta)):
         size, s1 = C.c_uint64(0), C.c_uint64(0)
         a = (out_d.data_ptr() + po[0], v.name_ulen, out_d.data_ptr() + po[1],
-             None if fa else out_d.data_ptr() + po[2], ln.ctypes.data, len(ln),
-             int(plus_name))
+             None if fa or not with_qual else out_d.data_ptr() + po[2], ln.ctypes.data, len(ln),
+             int(plus_name) if slices is None else slices[j])
         _check(fmt(*a, None, 0, C.byref(size), *((C.byref(s1),) if pairs else ())),
                "fqz5_fastq_format")
         args.append(a)
@@ -1392,6 +1428,7 @@ def _decode(data, buf, plus_name: bool, device: str, pairs: bool = False, ranges
         _check(fmt(*a, text.data_ptr() + at, n, C.byref(size),
                    *((C.byref(s1),) if pairs else ())), "fqz5_fastq_format")
         at += n
+    st_fmt.__exit__(None, None, None)
     if not pairs:
         return text[:at]
     idx1, idx2, at = [], [], 0
@@ -1647,3 +1684,227 @@ def _write_out(path: str, data) -> None:
     else:
         with open(path, "wb") as f:
             f.write(data)
+
+
+# ---------------------------------------------------------------------------
+# Record ranges through the block index
+#
+# The index at the end of the file (write_index, fqzcomp5.c:2606-2630) gives
+# every block's file offset and record count, so the blocks that hold records
+# [first, first + count) follow from prefix sums of the counts, and only those
+# blocks are read, checked and decoded (whole: a block's rANS streams, its
+# adaptive models and its tok3 names have no prefix decode).  Their text is
+# laid out on the device for the wanted records only
+# (fqz5_fastq_format_range).  The reference writes the index and reads it
+# only for --inspect; a file without one (v1.0 files written without, the
+# old headerless format) is walked block header by block header instead.
+# ---------------------------------------------------------------------------
+class Index(list):
+    """Blocks of a container as (start, end, nrec): the block's byte range
+    in the file and its record count; `version` as for Blocks, `indexed`
+    whether the file's own index gave them (else the block headers did)."""
+
+    def __init__(self, blocks=(), version: int = V11, indexed: bool = True):
+        super().__init__(blocks)
+        self.version, self.indexed = version, indexed
+
+
+class _PosBytes:
+    """A container held in memory, read at positions (as _PosFile)."""
+
+    def __init__(self, data):
+        self.mv = memoryview(data).cast("B")
+        self.size = len(self.mv)
+
+    def read(self, a: int, b: int) -> np.ndarray:
+        return np.frombuffer(self.mv[a:max(a, b)], np.uint8).copy()
+
+    def close(self) -> None:
+        pass
+
+
+def _reader(src):
+    """(reader, whether to close it): src a path, bytes, or a reader."""
+    import os
+    if isinstance(src, (str, os.PathLike)):
+        return _PosFile(os.fspath(src)), True
+    if hasattr(src, "read") and hasattr(src, "size"):
+        return src, False
+    return _PosBytes(src), False
+
+
+def read_index(src) -> Index:
+    """The blocks of a .fqz5 (a path, the file's bytes, or a positioned
+    reader) as an Index.  With an index offset in the header this is one
+    positioned read of the index and touches no block; the index is checked
+    structurally (magic, size, offsets from 16 strictly increasing up to the
+    index) and a failure raises ValueError("corrupt index: ...").  Without
+    one the block size fields are walked (_walk) and each block's record
+    count comes from its header."""
+    rd, close = _reader(src)
+    try:
+        size = rd.size
+        version, start, idx = _version_of(bytes(rd.read(0, min(16, size))), size)
+        if idx:
+            if idx == size == 16:
+                return Index(version=version)              # an empty body: no index is written
+            raw = bytes(rd.read(idx, size))                # the one read
+            if len(raw) < 12 or raw[:8] != INDEX_MAGIC:
+                raise ValueError("corrupt index: bad magic")
+            (n,) = struct.unpack_from("<I", raw, 8)
+            if 12 + 16 * n > len(raw):
+                raise ValueError("corrupt index: more entries than the file holds")
+            ent = [struct.unpack_from("<QII", raw, 12 + 16 * k) for k in range(n)]
+            offs = [e[0] for e in ent]
+            if (offs[0] != 16) if n else (idx != 16):
+                raise ValueError("corrupt index: the first block is not at offset 16")
+            if any(b <= a for a, b in zip(offs, offs[1:])):
+                raise ValueError("corrupt index: block offsets do not increase")
+            if n and offs[-1] >= idx:
+                raise ValueError("corrupt index: a block offset past the index")
+            ends = offs[1:] + [idx]
+            return Index([(o, e, ent[k][2]) for k, (o, e) in enumerate(zip(offs, ends))],
+                         version, True)
+        cnt = {}
+
+        def read4(p):
+            h = bytes(rd.read(p, min(p + 8, size)))
+            if len(h) == 8:
+                cnt[p] = struct.unpack_from("<I", h, 4)[0]
+            return h[:4]
+        blocks = _walk(read4, start, size, version)
+        return Index([(s, e, cnt[s]) for s, e in blocks], version, False)
+    finally:
+        if close:
+            rd.close()
+
+
+def cover(index, first: int, count: int) -> list[tuple[int, int, int]]:
+    """The blocks holding records [first, first + count) of the file, as
+    (block, first record within it, records from it), in file order.  The
+    range is clipped to the file's records; one starting at or past their
+    end covers nothing.  Python ints throughout: files hold more than 2^32
+    records."""
+    import bisect
+    if first < 0 or count < 0:
+        raise ValueError("cover: negative record range")
+    ends, tot = [], 0
+    for _, _, n in index:
+        tot += int(n)
+        ends.append(tot)
+    last = min(first + count, tot)
+    out = []
+    b = bisect.bisect_right(ends, first)          # the first block ending after `first`
+    while b < len(ends) and first < last:
+        b0 = ends[b] - int(index[b][2])
+        k = min(last, ends[b]) - first
+        if k:
+            out.append((b, first - b0, k))
+        first += k
+        b += 1
+    return out
+
+
+def _extract_windows(rd, first: int, count: int, plus_name: bool, device: str, pairs: bool,
+                     with_qual: bool, window_bytes: int | None):
+    """The text of records [first, first + count) (pairs: of pairs) of the
+    container behind `rd`, window by window: device tensors (pairs: the R1
+    and the R2 text)."""
+    import torch
+    mul = 2 if pairs else 1
+    with _stage("index"):
+        index = read_index(rd)
+        cov = cover(index, mul * first, mul * count)
+    wb = window_bytes or DEFAULT_WINDOW
+    groups, cur, tot = [], [], 0
+    for c in cov:
+        z = index[c[0]][1] - index[c[0]][0]
+        if cur and tot + z > wb:
+            groups.append(cur)
+            cur, tot = [], 0
+        cur.append(c)
+        tot += z
+    if cur:
+        groups.append(cur)
+    for grp in groups:
+        a, e = index[grp[0][0]][0], index[grp[-1][0]][1]      # (covering blocks are adjacent)
+        with _stage("read"):
+            hv = rd.read(a, e)
+            if len(hv) != e - a:
+                raise _lib.NativeError("index disagrees with the file: a block past its end")
+        for b, _, _ in grp:
+            s, t, n = index[b]
+            bsz, nrec = struct.unpack_from("<II", hv, s - a) if t - s >= 8 else (None, None)
+            if bsz != t - s - 4 or nrec != n:
+                raise _lib.NativeError(
+                    f"index disagrees with block {b}: size {bsz} records {nrec} in its header, "
+                    f"size {t - s - 4} records {n} in the index")
+        with _stage("upload"):
+            buf = torch.from_numpy(np.ascontiguousarray(hv)).to(device)   # blocking
+        texts = _decode(hv, buf, plus_name, device, pairs=pairs,
+                        ranges=Blocks([(index[b][0] - a, index[b][1] - a) for b, _, _ in grp],
+                                      index.version),
+                        slices=[(rf, rc) for _, rf, rc in grp], with_qual=with_qual)
+        yield texts if pairs else (texts,)
+        del buf, hv, texts
+
+
+def extract_bytes(data, first: int, count: int, plus_name: bool = False, device: str = "cuda",
+                  with_qual: bool = True) -> bytes:
+    """Records [first, first + count) of a .fqz5 held in memory, as the
+    text decompress_bytes gives for them: only the blocks that hold them
+    (read_index, cover) are uploaded, checked and decoded.  with_qual False:
+    the quality sections are not decoded and the text is FASTA ('>' name,
+    sequence), as for a FASTA block either way."""
+    out = [t[0].cpu().numpy().tobytes()
+           for t in _extract_windows(_PosBytes(data), first, count, plus_name, device, False,
+                                     with_qual, None)]
+    _trace_dump("extract")
+    return b"".join(out)
+
+
+def extract_file(src: str, dst: str, first: int, count: int, plus_name: bool = False,
+                 device: str = "cuda", dst2: str | None = None, with_qual: bool = True,
+                 window_bytes: int | None = None) -> int:
+    """Records [first, first + count) of the .fqz5 file src to dst, reading
+    and decoding only the blocks that hold them: the index (one positioned
+    read; the block headers of a file without one), then the covering blocks
+    in windows of at most `window_bytes` of compressed data, each block
+    checked against its index entry, CRC-checked and decoded whole, its text
+    laid out on the GPU for the wanted records only.  dst2: first and count
+    are in pairs, records 2 first .. 2 (first + count) deinterleaved to dst
+    (R1) and dst2 (R2) as decompress_file(dst2=) does.  with_qual False: no
+    quality section is decoded and the text is FASTA.  A ".gz" destination is
+    gzip-compressed.  One process; returns the text bytes written."""
+    pairs = dst2 is not None
+    outs = [dst] + ([dst2] if pairs else [])
+    # plain outputs by positioned writes as the windows come, gzip ones whole
+    sinks = [None if d.endswith(".gz") else _Sink(d, True) for d in outs]
+    held = [[] for _ in outs]
+    written = [0 for _ in outs]
+    rd = _PosFile(src)
+    try:
+        for texts in _extract_windows(rd, first, count, plus_name, device, pairs, with_qual,
+                                      window_bytes):
+            for j, t in enumerate(texts):
+                with _stage("download"):
+                    out = _pinned(int(t.numel()))
+                    out.copy_(t)
+                with _stage("write"):
+                    if sinks[j] is not None:
+                        sinks[j].write_at(written[j], out.numpy())
+                    else:
+                        held[j].append(out.numpy().tobytes())
+                    written[j] += int(t.numel())
+                del out
+    finally:
+        rd.close()
+        for sk in sinks:
+            if sk is not None:
+                sk.close()
+    with _stage("write"):
+        for d, sk, h in zip(outs, sinks, held):
+            if sk is None:
+                _write_out(d, b"".join(h))
+    _trace_dump("extract")
+    return sum(written)

@@ -23,6 +23,9 @@
  *                       block: '@' name '\n' seq '\n' '+' [name] '\n'
  *                       qual + 33 '\n'; without qualities output_fasta
  *                       (:3503-3517): '>' name '\n' seq '\n'.
+ *   fqz5_fastq_format_range  the same text for a range of a block's records
+ *                       only (record ranges read through the file's block
+ *                       index, fqz5file.extract_file), laid out on the device.
  *
  * Offsets are bytes into the text.  Calls return 0 (fqz5_fastq_index: 1 for
  * FASTA text; fqz5_fastq_blocks: the block count) or -1 with
@@ -96,6 +99,23 @@ int fqz5_fastq_format(const uint8_t *d_names, uint64_t name_len, const uint8_t *
 int fqz5_fastq_format_pairs(const uint8_t *d_names, uint64_t name_len, const uint8_t *d_seq,
                             const uint8_t *d_qual, const uint32_t *h_len, uint64_t nrec,
                             int plus_name, uint8_t *d_out, uint64_t out_cap, uint64_t *out_len,
+                            uint64_t *r1_len);
+
+/* The text of records [rec_first, rec_first + rec_count) of a block alone:
+ * exactly the bytes fqz5_fastq_format (pairs != 0: fqz5_fastq_format_pairs,
+ * the slice's even records of the block first, its odd ones after them;
+ * *r1_len, may be NULL, the first part's size) writes for those records, the
+ * slice's first record at d_out[0].  d_names, name_len, d_seq, d_qual, h_len
+ * and nrec are the whole block's, as for fqz5_fastq_format (h_len is read up
+ * to the slice end); the caller clips the slice: rec_first + rec_count > nrec
+ * fails, as do fewer name terminators than rec_first + rec_count and a text
+ * larger than out_cap.  rec_count 0: *out_len = 0, nothing is launched.
+ * d_out NULL: the sizes only.  The layout (record sizes, output and sequence
+ * offsets) is computed on the device by scans; only the totals come back. */
+int fqz5_fastq_format_range(const uint8_t *d_names, uint64_t name_len, const uint8_t *d_seq,
+                            const uint8_t *d_qual, const uint32_t *h_len, uint64_t nrec,
+                            uint64_t rec_first, uint64_t rec_count, int plus_name, int pairs,
+                            uint8_t *d_out, uint64_t out_cap, uint64_t *out_len,
                             uint64_t *r1_len);
 
 #ifdef __cplusplus
