@@ -336,6 +336,18 @@ void fqz5_decode_chain_counts(uint64_t *out2) {
     out2[1] = g_chains_gpu.load();
 }
 
+void fqz5_rans_chain_counts(uint64_t *out2) { rans_chain_counts(out2); }
+
+void fqz5_host_plan(const uint64_t *n, const int *kind, int count, int threads,
+                    const double *core_ns, char *on_host) {
+    const std::vector<uint64_t> nv(n, n + count);
+    const std::vector<int> kv(kind, kind + count);
+    std::vector<double> cores;
+    if (core_ns) cores.assign(core_ns, core_ns + threads);
+    const std::vector<char> on = host::plan(nv, kv, threads, core_ns ? &cores : nullptr);
+    std::copy(on.begin(), on.end(), on_host);
+}
+
 void fqz5_trial_counts(uint64_t *out2) {
     out2[0] = g_fqz_tried.load();
     out2[1] = g_fqz_pruned.load();
@@ -1253,7 +1265,13 @@ int fqz5_decode_sections(const fqz5_section *secs, int nsec, fqz5_section_result
             });
         }
         Join join_seq{ts};
-        decompress_batch(g, reqs);
+        // the rANS batch's long chains share the cores with the chains
+        // started above: it gets the cores those leave idle (the late
+        // quality chains run after it), so that no more than host::threads()
+        // chain threads of this call run at once
+        host::CoreBudget cores;
+        cores.core_ns.assign(size_t(host::threads()) - std::min(size_t(host::threads()), hjobs.running()), 0.0);
+        decompress_batch(g, reqs, &cores);
         const double t_rans = trace ? now_ms() : 0;
         if (trace)
             std::fprintf(stderr, "decode_sections: %zu bytes to host in %.1f ms, rANS %.1f ms\n", tot,

@@ -10,7 +10,9 @@
 // these chains here, on a pool of host threads beside the GPU's rANS and name
 // work, when the host mode asks for it (fqz5_set_host_decode).  Same inputs,
 // same bytes as the GPU decoders (tests/test_host_dec.py checks both against
-// the reference's vectors).
+// the reference's vectors).  The placement plan at the end of this file
+// (plan, chain_ns, chain_measured) also serves the plain rANS 4x16 chains of
+// host_rans.cpp, which rans_decompress.cpp places the same way.
 //
 // Models (own layout, reference arithmetic): an adaptive list per context
 // (c_simple_model.h: freq +16, halved past 65519, one bubble step per
@@ -357,11 +359,19 @@ int seq_decode(const uint8_t *in, uint32_t in_size, const uint32_t *lens, int nr
 }
 
 namespace {
+// the plain rANS decoders of host_rans.cpp on one host core, ns per symbol:
+// measured on the MI355X box's cores with 16 chains at once, the -3 bench's
+// 44.5 M-symbol sequence chains and 22 M-symbol packed qualities
+// (profiles/hostrans_step_trace.txt: 0.92-0.98 and 1.36-1.39)
+constexpr double HOST_RANS_O0_NS = 1.0, HOST_RANS_O1_NS = 1.4;
 // ns per symbol [kind][gpu]: priors from r04 on MI355X boxes (host: this
 // file's decoders on one core of the box, the -5 Illumina hybrid step; GPU:
 // k_fqz_dec_small 170-190, the general decoder with sequence contexts
-// 350-470, k_seq_dec 290-380)
-std::atomic<double> g_ns[CK_N][2] = {{{30.0}, {330.0}}, {{16.0}, {180.0}}, {{24.0}, {400.0}}};
+// 350-470, k_seq_dec 290-380).  The plain rANS 4x16 chains: GPU 54.4 ns a
+// step of 4 symbols for order-0 and 73.4 for order-1;
+// host: HOST_RANS_O0_NS / _O1_NS above
+std::atomic<double> g_ns[CK_N][2] = {{{30.0}, {330.0}}, {{16.0}, {180.0}}, {{24.0}, {400.0}},
+                                     {{HOST_RANS_O0_NS}, {13.6}}, {{HOST_RANS_O1_NS}, {18.4}}};
 }  // namespace
 
 double chain_ns(int kind, bool gpu) { return g_ns[kind][gpu ? 1 : 0].load(std::memory_order_relaxed); }
@@ -374,7 +384,8 @@ void chain_measured(int kind, bool gpu, double ns) {
     while (!a.compare_exchange_weak(cur, 0.5 * cur + 0.5 * ns, std::memory_order_relaxed)) {}
 }
 
-std::vector<char> plan(const std::vector<uint64_t> &n, const std::vector<int> &kind, int threads) {
+std::vector<char> plan(const std::vector<uint64_t> &n, const std::vector<int> &kind, int threads,
+                       const std::vector<double> *core_ns, std::vector<double> *committed) {
     std::vector<char> host(n.size(), 0);
     std::vector<size_t> ord(n.size());
     for (size_t i = 0; i < ord.size(); i++) ord[i] = i;
@@ -382,6 +393,11 @@ std::vector<char> plan(const std::vector<uint64_t> &n, const std::vector<int> &k
         return double(n[a]) * chain_ns(kind[a], false) > double(n[b]) * chain_ns(kind[b], false);
     });
     std::vector<double> core(size_t(std::max(threads, 1)), 0.0);   // each core's finish time
+    if (core_ns) core = *core_ns;
+    if (core.empty()) {                      // no core to give: every chain on the GPU
+        if (committed) committed->clear();
+        return host;
+    }
     double gpu_t = 0.0;
     for (size_t i : ord) {
         auto lo = std::min_element(core.begin(), core.end());
@@ -398,6 +414,7 @@ std::vector<char> plan(const std::vector<uint64_t> &n, const std::vector<int> &k
             gpu_t = std::max(gpu_t, tg);
         }
     }
+    if (committed) *committed = core;
     return host;
 }
 

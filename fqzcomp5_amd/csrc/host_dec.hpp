@@ -1,4 +1,6 @@
-// host_dec.hpp — the adaptive-model decode chains on host cores (host_dec.cpp)
+// host_dec.hpp — the serial decode chains on host cores: the adaptive-model
+// decoders and the placement of every chain kind (host_dec.cpp); the plain
+// rANS 4x16 decoders are in host_rans.hpp
 #pragma once
 #include <atomic>
 #include <cstddef>
@@ -32,32 +34,49 @@ int threads();
 // the cores share above without the cap of 16
 int cores_of_rank();
 
-// Which adaptive-model decode chains of a fqz5_decode_sections call run on
-// host cores and which on the GPU (host_decode_mode() 2, the default).  A
-// chain is serial whichever side runs it: on a host core it costs
-// n x host_ns, and a host core takes one chain at a time; on the GPU each
-// chain has a wave of its own (the launch lasts as long as its longest
-// chain, n x gpu_ns).  The per-symbol costs start at committed measurements
-// (profiles/r04_fqz_dec_bench.txt) and follow what this
-// process measures: every host chain's time, and every GPU batch's time over
-// its longest chain.  plan() places the chains longest first, each where the
-// call's finish time (the later of the host cores' and the GPU's) grows
-// least; ties go to the host.
-enum ChainKind { CK_SEQ = 0, CK_FQZ = 1, CK_FQZ_SEQ = 2, CK_N };
+// Which decode chains run on host cores and which on the GPU
+// (host_decode_mode() 2, the default): the adaptive-model chains of a
+// fqz5_decode_sections call (CK_SEQ, CK_FQZ, CK_FQZ_SEQ), and the plain rANS
+// 4x16 order-0 / order-1 chains of every decompress_batch (CK_RANS_O0,
+// CK_RANS_O1; rans_decompress.cpp run_djs).  A chain is serial whichever
+// side runs it: on a host core it costs n x host_ns, and a host core takes
+// one chain at a time; on the GPU each chain has a wave of its own (the
+// launch lasts as long as its longest chain, n x gpu_ns).  The per-symbol
+// costs start at committed measurements (profiles/r04_fqz_dec_bench.txt,
+// DESIGN.md section 4) and follow what this process measures: every host
+// chain's time, and every GPU batch's time over its longest chain (chains of
+// 2^20 symbols and more only).  plan() places the chains longest first, each
+// where the call's finish time (the later of the host cores' and the GPU's)
+// grows least; ties go to the host.  core_ns: the cores' finish times (ns)
+// before these chains, i.e. what an earlier plan of the same call committed
+// (nullptr: `threads` idle cores); committed, when given, receives the cores'
+// finish times after them.
+enum ChainKind { CK_SEQ = 0, CK_FQZ = 1, CK_FQZ_SEQ = 2, CK_RANS_O0 = 3, CK_RANS_O1 = 4, CK_N };
 double chain_ns(int kind, bool gpu);
 void chain_measured(int kind, bool gpu, double ns_per_symbol);
-std::vector<char> plan(const std::vector<uint64_t> &n, const std::vector<int> &kind, int threads);
+std::vector<char> plan(const std::vector<uint64_t> &n, const std::vector<int> &kind, int threads,
+                       const std::vector<double> *core_ns = nullptr,
+                       std::vector<double> *committed = nullptr);
 
-// fn(i) for i in [0, n) on up to threads() host threads, started by start()
-// and waited for by join() (or the destructor); the work list is shared, so
-// long and short jobs balance.
+// The host cores a decompress_batch may give its rANS chains within a
+// fqz5_decode_sections call: the cores not running that call's
+// adaptive-model chains, with their finish times (ns; all zero: idle).  A
+// call without one plans against threads() idle cores.
+struct CoreBudget {
+    std::vector<double> core_ns;
+};
+
+// fn(i) for i in [0, n) on up to threads() host threads (max_threads, when
+// given, lowers that), started by start() and waited for by join() (or the
+// destructor); the work list is shared, so long and short jobs balance.
 class Jobs {
   public:
-    void start(size_t n, std::function<void(size_t)> fn) {
+    void start(size_t n, std::function<void(size_t)> fn, size_t max_threads = 0) {
         fn_ = std::move(fn);
         n_ = n;
         next_ = 0;
-        const size_t t = std::min<size_t>(n, size_t(threads()));
+        size_t t = std::min<size_t>(n, size_t(threads()));
+        if (max_threads) t = std::min(t, max_threads);
         for (size_t k = 0; k < t; k++)
             th_.emplace_back([this] {
                 for (size_t i; (i = next_.fetch_add(1)) < n_;) fn_(i);
@@ -67,6 +86,7 @@ class Jobs {
         for (auto &t : th_) t.join();
         th_.clear();
     }
+    size_t running() const { return th_.size(); }
     ~Jobs() { join(); }
 
   private:

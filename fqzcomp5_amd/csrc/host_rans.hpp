@@ -1,0 +1,50 @@
+// host_rans.hpp — plain rANS 4x16 entropy chains on a host core (host_rans.cpp)
+//
+// The same streams, bytes and ok / failed verdicts as k_rans_dec's NX = 4
+// bodies (rans_chain.hip dec4_*): an order-0 or order-1 chain of 4
+// interleaved states over 16-bit words.  One chain is serial whoever runs it;
+// a host core steps it several times faster than a GPU wave, and
+// Decompressor::run_djs (rans_decompress.cpp) places the long ones here by
+// the cost model of host_dec.hpp.  No HIP in this file or its .cpp.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+namespace fqz5 {
+namespace host {
+
+// The stream's frequency tables as the planner parses them
+// (Decompressor::DJ): F rows x 256 normalised to 2^bits per non-empty row.
+// Order-0: one row, bits 12.  Order-1: one row per context of `alpha`
+// (ascending, alpha[0] == 0), a row of zeros for a context that never
+// occurs.
+// decode_freq + normalise_freq_shift of an order-0 table at [p, end):
+// *used = its bytes.
+bool rans_parse_o0(const uint8_t *p, const uint8_t *end, std::vector<uint32_t> &F, uint32_t *used);
+// decode_freq1 of an (uncompressed) order-1 table at [p, end) for 2^bits
+// slots: *used = its bytes.
+bool rans_parse_o1(const uint8_t *p, const uint8_t *end, int bits, std::vector<uint32_t> &F,
+                   std::vector<uint8_t> &alpha, uint32_t *used);
+
+// n symbols from `in` (the 4 states, then the words; in_len bytes to the
+// stream's end) into out[0, n).  True = the GPU decoder's status 0: the
+// chain consumed no more words than the stream has.  Reads stay inside
+// [in, in + in_len), writes inside [out, out + n).
+bool rans_dec_o0(const uint32_t *F, int bits, const uint8_t *in, size_t in_len, uint8_t *out,
+                 size_t n);
+// split_table: the stream's table takes the GPU decoder's split layout
+// (kernels.h dec_table_mode == DEC_TAB_SPLIT), which differs from the others
+// only in what a damaged stream decodes from a context without a row.
+bool rans_dec_o1(const uint32_t *F, const uint8_t *alpha, size_t rows, int bits, bool split_table,
+                 const uint8_t *in, size_t in_len, uint8_t *out, size_t n);
+
+// A whole rans_compress_4x16 stream whose order byte has only the order-1
+// and NOSZ bits set (a compressed order-1 table is decoded here too);
+// out_cap is the size itself for a NOSZ stream.  0, or -1 for any other
+// stream and for a damaged one.
+int rans_dec_stream(const uint8_t *in, size_t in_size, uint8_t *out, size_t out_cap,
+                    size_t *out_size);
+
+}  // namespace host
+}  // namespace fqz5

@@ -93,7 +93,12 @@ struct DecompressReq {
     uint32_t out_size = 0;
 };
 
-// rans_uncompress_to_4x16 semantics.
-void decompress_batch(GpuCtx &g, std::vector<DecompressReq> &reqs);
+// rans_uncompress_to_4x16 semantics.  cores: the host cores the batch may
+// give its long rANS chains (host_dec.hpp; nullptr: host::threads() idle ones).
+namespace host { struct CoreBudget; }
+void decompress_batch(GpuCtx &g, std::vector<DecompressReq> &reqs,
+                      const host::CoreBudget *cores = nullptr);
+// entropy chains of stage B placed so far: out2[0] on host cores, out2[1] on the GPU
+void rans_chain_counts(uint64_t *out2);
 
 }  // namespace fqz5

@@ -6,6 +6,11 @@
 //   A  O0 chains of compressed order-1 tables   (only when present)
 //   B  all O0 / O1 chains (main data and RLE meta-data)
 //   C  RLE expansion, D  un-packing, E  stripe interleave.
+// A chain of stage B with 4 states may instead decode on a host core
+// (host_rans.cpp) beside the launch, where the cost model of host_dec.hpp
+// finishes the batch sooner (run_djs); its bytes are uploaded in stream order
+// before stages C-E.
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -13,6 +18,8 @@
 #include <climits>
 #include <cstring>
 
+#include "host_dec.hpp"
+#include "host_rans.hpp"
 #include "kernels.h"
 #include "rans_codec.hpp"
 #include "rans_format.hpp"
@@ -69,13 +76,17 @@ struct Node {
 
 class Decompressor {
   public:
-    explicit Decompressor(GpuCtx &g) : g_(g) {}
+    Decompressor(GpuCtx &g, const host::CoreBudget *cores) : g_(g), cores_(cores) {}
     void run(std::vector<DecompressReq> &reqs);
 
   private:
     GpuCtx &g_;
+    const host::CoreBudget *cores_;     // nullptr: host::threads() idle cores
     std::vector<Node> nodes_;
     std::vector<DJ> djs_;
+    // (trace) stage B's host chains and how long their join took after the launch
+    size_t host_chains_ = 0;
+    double host_join_ms_ = 0, host_longest_ms_ = 0;
 
     int parse(const uint8_t *h, const uint8_t *d, uint32_t len, uint8_t *d_out,
               uint32_t out_cap, int depth);
@@ -83,7 +94,7 @@ class Decompressor {
                int nx, uint8_t *d_out);
     bool parse_o0_table(DJ &j, const uint8_t *p, const uint8_t *end, uint32_t *used);
     bool parse_o1_table(DJ &j, const uint8_t *p, const uint8_t *end);
-    void run_djs(const std::vector<int> &ids);
+    void run_djs(const std::vector<int> &ids, bool may_host);
 };
 
 int Decompressor::add_dj(const uint8_t *h, const uint8_t *d, uint32_t len, uint32_t n,
@@ -126,46 +137,16 @@ int Decompressor::add_dj(const uint8_t *h, const uint8_t *d, uint32_t len, uint3
 // decode_freq + normalise_freq_shift (rANS_static4x16pr.c:261-285)
 bool Decompressor::parse_o0_table(DJ &j, const uint8_t *p, const uint8_t *end,
                                   uint32_t *used) {
-    uint32_t F[256] = {0}, tot = 0;
-    int k = get_freq0(p, end, F, &tot);
-    if (!k) return false;
-    scale_pow2(F, tot, 4096);
-    uint32_t x = 0;
-    for (int s = 0; s < 256; s++) x += F[s];
-    if (x != 4096) return false;
     j.bits = 12;
-    j.F.assign(F, F + 256);
-    *used = uint32_t(k);
-    return true;
+    return host::rans_parse_o0(p, end, j.F, used);
 }
 
 // decode_freq1 (rANS_static16_int.h:468-536).  Sets tab_len for the
 // uncompressed case.
 bool Decompressor::parse_o1_table(DJ &j, const uint8_t *p0, const uint8_t *end) {
-    const uint8_t *p = p0;
-    uint32_t A[256] = {0};
-    int k = get_alphabet(p, end, A);
-    if (!k) return false;
-    p += k;
-    if (p >= end) return false;
-    j.alpha.clear();
-    for (int s = 0; s < 256; s++)
-        if (A[s]) j.alpha.push_back(uint8_t(s));
-    if (j.alpha.empty() || j.alpha[0] != 0) return false;
-    j.F.assign(j.alpha.size() * 256, 0);
-    for (size_t r = 0; r < j.alpha.size(); r++) {
-        uint32_t F[256] = {0}, T = 0;
-        k = get_freq_row(p, end, A, F, &T);
-        if (!k) return false;
-        p += k;
-        if (!T) continue;
-        scale_pow2(F, T, 1u << j.bits);
-        uint32_t x = 0;
-        for (int s = 0; s < 256; s++) x += F[s];
-        if (x != (1u << j.bits)) return false;
-        std::memcpy(&j.F[r * 256], F, sizeof F);
-    }
-    if (j.hdr_dj < 0) j.tab_len = 1 + uint32_t(p - p0);
+    uint32_t used = 0;
+    if (!host::rans_parse_o1(p0, end, j.bits, j.F, j.alpha, &used)) return false;
+    if (j.hdr_dj < 0) j.tab_len = 1 + used;
     return true;
 }
 
@@ -338,7 +319,97 @@ static bool o1_keys(const DJ &j, DecJob &d) {
     return true;
 }
 
-void Decompressor::run_djs(const std::vector<int> &ids) {
+// $FQZ5_STEP_TRACE: host wall time of the decode phases on stderr
+static bool step_trace() {
+    static const bool on = std::getenv("FQZ5_STEP_TRACE") != nullptr;
+    return on;
+}
+static double now_ms() {
+    return std::chrono::duration<double, std::milli>(
+               std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+std::atomic<uint64_t> g_rans_host{0}, g_rans_gpu{0};   // fqz5_rans_chain_counts
+
+// a chain's kind for the cost model, and the chains too short to be worth a
+// core: under 2^20 symbols a chain costs the launch under ~20 ms beside the
+// others
+constexpr uint32_t HOST_CHAIN_MIN = 1u << 20;
+inline int chain_kind(const DJ &j) { return j.o1 ? host::CK_RANS_O1 : host::CK_RANS_O0; }
+
+void Decompressor::run_djs(const std::vector<int> &ids, bool may_host) {
+    // ---- the chains that decode on host cores (host_decode_mode(): 0 none,
+    // 1 every 4-state chain, 2 by host::plan among those of 2^20 symbols and
+    // more, 3 every other one).  They start now, into pinned staging, and
+    // are joined after the launch below.
+    struct HostChain { int id; uint8_t *buf; bool ok; double ns; };
+    std::vector<HostChain> hc;
+    std::vector<char> on_host(djs_.size(), 0);
+    size_t host_threads = 0;
+    const int hmode = may_host ? host_decode_mode() : 0;
+    if (hmode) {
+        std::vector<int> el;                     // eligible chains
+        for (int id : ids) {
+            const DJ &j = djs_[id];
+            if (!j.ok || !j.n || j.nx != 4 || j.len < j.tab_len + 16u) continue;
+            if (hmode == 2 && j.n < HOST_CHAIN_MIN) continue;
+            el.push_back(id);
+        }
+        std::vector<double> idle(size_t(host::threads()), 0.0);
+        const std::vector<double> &cores = cores_ ? cores_->core_ns : idle;
+        host_threads = cores.size();
+        if (hmode == 2 && !el.empty()) {
+            std::vector<uint64_t> n;
+            std::vector<int> kind;
+            for (int id : el) { n.push_back(djs_[id].n); kind.push_back(chain_kind(djs_[id])); }
+            const std::vector<char> on = host::plan(n, kind, int(cores.size()), &cores);
+            for (size_t k = 0; k < el.size(); k++) on_host[el[k]] = on[k];
+        } else if (host_threads) {
+            for (size_t k = 0; k < el.size(); k++) on_host[el[k]] = hmode == 1 || k % 2 == 0;
+        }
+        for (int id : el)
+            if (on_host[id]) hc.push_back({id, g_.staging.alloc(size_t(djs_[id].n) + 1), false, 0.0});
+        // the threads take them longest first, as the plan placed them
+        auto cost = [&](const HostChain &c) {
+            return double(djs_[c.id].n) * host::chain_ns(chain_kind(djs_[c.id]), false);
+        };
+        std::stable_sort(hc.begin(), hc.end(),
+                         [&](const HostChain &a, const HostChain &b) { return cost(a) > cost(b); });
+    }
+    host::Jobs hjobs;
+    hjobs.start(hc.size(), [&](size_t k) {
+        HostChain &c = hc[k];
+        const DJ &j = djs_[c.id];
+        const auto a = std::chrono::steady_clock::now();
+        const uint8_t *in = j.h + j.tab_len;
+        const size_t in_len = j.len - j.tab_len;
+        if (j.o1) {
+            const uint32_t rows = uint32_t(j.alpha.size());
+            c.ok = host::rans_dec_o1(j.F.data(), j.alpha.data(), rows, j.bits,
+                                     dec_table_mode(true, rows, j.bits) == DEC_TAB_SPLIT, in, in_len,
+                                     c.buf, j.n);
+        } else {
+            c.ok = host::rans_dec_o0(j.F.data(), j.bits, in, in_len, c.buf, j.n);
+        }
+        c.ns = std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - a).count();
+    }, host_threads);
+    // joined, judged and uploaded behind the launch in stream order
+    auto finish_host = [&] {
+        if (hc.empty()) return;
+        const double t0 = now_ms();
+        hjobs.join();
+        host_join_ms_ += now_ms() - t0;
+        host_chains_ += hc.size();
+        for (HostChain &c : hc) {
+            DJ &j = djs_[c.id];
+            host_longest_ms_ = std::max(host_longest_ms_, c.ns * 1e-6);
+            if (!c.ok) { j.ok = false; continue; }
+            if (j.n >= HOST_CHAIN_MIN) host::chain_measured(chain_kind(j), false, c.ns / double(j.n));
+            FQZ5_HIP(hipMemcpyAsync(j.d_out, c.buf, j.n, hipMemcpyHostToDevice, g_.stream));
+        }
+    };
+    g_rans_host += hc.size();
+
     std::vector<uint32_t> tabs;
     std::vector<uint8_t> alphas;
     struct Off { size_t tab, alpha; };
@@ -347,7 +418,7 @@ void Decompressor::run_djs(const std::vector<int> &ids) {
     // table image offsets first, then every job's table in parallel
     for (int id : ids) {
         DJ &j = djs_[id];
-        if (!j.ok || !j.n) continue;
+        if (!j.ok || !j.n || on_host[id]) continue;
         const size_t rows = j.o1 ? j.alpha.size() : 1;
         const uint32_t mode = dec_table_mode(j.o1, uint32_t(rows), j.bits);
         Off o{tabs.size(), alphas.size()};
@@ -388,7 +459,10 @@ void Decompressor::run_djs(const std::vector<int> &ids) {
             }
         }
     });
-    if (used.empty()) return;
+    if (used.empty()) {
+        finish_host();
+        return;
+    }
     const uint32_t *d_tabs = g_.upload(tabs);
     const uint8_t *d_alpha = alphas.empty() ? nullptr : g_.upload(alphas);
     int32_t *d_status = g_.arena.alloc_n<int32_t>(used.size());
@@ -468,11 +542,22 @@ void Decompressor::run_djs(const std::vector<int> &ids) {
         }
     }
     lds = g_.chain_lds(lds, djs.size());
+    g_rans_gpu += ord.size();
+    const auto launch_t0 = std::chrono::steady_clock::now();
     if (!djs.empty()) FQZ5_HIP(launch_dec(g_.upload(djs), int(djs.size()), lds, g_.stream));
     ev.stop(g_.stream);
     std::vector<int32_t> st(used.size());
     g_.download(st.data(), d_status, st.size());
     g_.sync();
+    // the launch's time over its longest chain: the GPU cost of that chain's kind
+    if (!ord.empty()) {
+        const DJ &lj = djs_[used[ord[0]]];
+        if (lj.nx == 4 && lj.n >= HOST_CHAIN_MIN)
+            host::chain_measured(chain_kind(lj), true,
+                                 std::chrono::duration<double, std::nano>(
+                                     std::chrono::steady_clock::now() - launch_t0).count() / double(lj.n));
+    }
+    finish_host();
     if (ev.on) {
         const double ms = ev.ms();
         g_.prof.dec_ms += ms;
@@ -482,16 +567,6 @@ void Decompressor::run_djs(const std::vector<int> &ids) {
     }
     for (size_t k = 0; k < used.size(); k++)
         if (st[k]) djs_[used[k]].ok = false;
-}
-
-// $FQZ5_STEP_TRACE: host wall time of the decode phases on stderr
-static bool step_trace() {
-    static const bool on = std::getenv("FQZ5_STEP_TRACE") != nullptr;
-    return on;
-}
-static double now_ms() {
-    return std::chrono::duration<double, std::milli>(
-               std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 void Decompressor::run(std::vector<DecompressReq> &reqs) {
@@ -508,7 +583,7 @@ void Decompressor::run(std::vector<DecompressReq> &reqs) {
     for (size_t i = 0; i < djs_.size(); i++)
         if (djs_[i].hdr_dj >= 0) hdr.push_back(djs_[i].hdr_dj);
     if (!hdr.empty()) {
-        run_djs(hdr);
+        run_djs(hdr, false);                     // (short chains: always the GPU)
         for (size_t i = 0; i < djs_.size(); i++) {
             DJ &j = djs_[i];
             if (j.hdr_dj < 0) continue;
@@ -531,7 +606,7 @@ void Decompressor::run(std::vector<DecompressReq> &reqs) {
     for (size_t i = 0; i < djs_.size(); i++)
         if (!is_hdr[i]) rest.push_back(int(i));
     const double t2 = step_trace() ? now_ms() : 0;
-    run_djs(rest);
+    run_djs(rest, true);
     const double t3 = step_trace() ? now_ms() : 0;
 
     // CAT payloads
@@ -713,8 +788,13 @@ void Decompressor::run(std::vector<DecompressReq> &reqs) {
     g_.sync();
     if (step_trace())
         std::fprintf(stderr, "decode: parse %.1f ms, o1 headers %.1f ms, chains %.1f ms, "
-                     "post %.1f ms (%zu streams, %zu chains)\n", t1 - t0, t2 - t1, t3 - t2,
-                     now_ms() - t3, reqs.size(), djs_.size());
+                     "post %.1f ms (%zu streams, %zu chains; %zu on host cores, the longest "
+                     "%.1f ms, joined %.1f ms after the launch; ns per symbol host / GPU: "
+                     "O0 %.2f / %.2f, O1 %.2f / %.2f)\n", t1 - t0, t2 - t1, t3 - t2,
+                     now_ms() - t3, reqs.size(), djs_.size(), host_chains_, host_longest_ms_,
+                     host_join_ms_, host::chain_ns(host::CK_RANS_O0, false),
+                     host::chain_ns(host::CK_RANS_O0, true), host::chain_ns(host::CK_RANS_O1, false),
+                     host::chain_ns(host::CK_RANS_O1, true));
     for (size_t i = 0; i < reqs.size(); i++) {
         Node &N = nodes_[roots[i]];
         reqs[i].ok = N.ok;
@@ -724,9 +804,14 @@ void Decompressor::run(std::vector<DecompressReq> &reqs) {
 
 }  // namespace
 
-void decompress_batch(GpuCtx &g, std::vector<DecompressReq> &reqs) {
-    Decompressor d(g);
+void decompress_batch(GpuCtx &g, std::vector<DecompressReq> &reqs, const host::CoreBudget *cores) {
+    Decompressor d(g, cores);
     d.run(reqs);
+}
+
+void rans_chain_counts(uint64_t *out2) {
+    out2[0] = g_rans_host.load();
+    out2[1] = g_rans_gpu.load();
 }
 
 }  // namespace fqz5

@@ -227,6 +227,45 @@ def rans_uncompress(comp: bytes) -> bytes:
     return out
 
 
+def rans_chain_counts() -> tuple[int, int]:
+    """Plain rANS chains placed so far: (on host cores, on the GPU)."""
+    c = (C.c_uint64 * 2)()
+    so = load()
+    so.fqz5_rans_chain_counts.restype = None
+    so.fqz5_rans_chain_counts.argtypes = [C.POINTER(C.c_uint64)]
+    so.fqz5_rans_chain_counts(c)
+    return int(c[0]), int(c[1])
+
+
+def rans_dec_host(comp: bytes, cap: int) -> bytes | None:
+    """fqz5_rans_dec_host: a plain order-0 / order-1 4x16 stream on a host
+    core (no GPU); None where it fails or refuses the order byte."""
+    buf = C.create_string_buffer(max(cap, 1))
+    n = C.c_size_t(0)
+    so = load()
+    so.fqz5_rans_dec_host.restype = C.c_int
+    so.fqz5_rans_dec_host.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                      C.POINTER(C.c_size_t)]
+    if so.fqz5_rans_dec_host(bytes(comp), len(comp), buf, cap, C.byref(n)):
+        return None
+    return buf.raw[:n.value]
+
+
+def host_plan(n, kind, threads: int, core_ns=None) -> list[int]:
+    """host::plan: 1 per chain placed on a host core, 0 for the GPU."""
+    cnt = len(n)
+    na = (C.c_uint64 * max(cnt, 1))(*[int(x) for x in n])
+    ka = (C.c_int * max(cnt, 1))(*[int(x) for x in kind])
+    ca = None if core_ns is None else (C.c_double * threads)(*[float(x) for x in core_ns])
+    out = C.create_string_buffer(max(cnt, 1))
+    so = load()
+    so.fqz5_host_plan.restype = None
+    so.fqz5_host_plan.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_int, C.c_int,
+                                  C.POINTER(C.c_double), C.c_char_p]
+    so.fqz5_host_plan(na, ka, cnt, threads, ca, out)
+    return [out.raw[i] for i in range(cnt)]
+
+
 def rans_uncompress_to(comp: bytes, size: int) -> bytes | None:
     lib = load()
     buf = C.create_string_buffer(max(size, 1))

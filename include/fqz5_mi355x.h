@@ -157,8 +157,14 @@ char *fqz5_seq_decode_host(unsigned char *in, unsigned int in_size, unsigned int
  * 1 = on host cores (up to $FQZ5_HOST_THREADS threads) beside the GPU's
  * rANS, LZP and name work, 2 = each chain where its measured cost finishes
  * the call soonest (the default; $FQZ5_HOST_DECODE overrides it); 3 =
- * every other chain on host cores (tests of the mixed placement).  Output
- * bytes do not depend on it.  Returns the previous setting. */
+ * every other chain on host cores (tests of the mixed placement).  The same
+ * setting places the plain rANS 4x16 order-0 / order-1 chains of every
+ * decoder call (rans_uncompress_*, the block decoder's rANS sections and
+ * names): 0 = the GPU, 1 = every such chain on host cores, 2 = by cost among
+ * the chains of 2^20 symbols and more (shorter ones stay on the GPU), 3 =
+ * every other one.  32-state (X32) chains and the small chain of a compressed
+ * order-1 table always decode on the GPU.  Output bytes and the verdict on a
+ * damaged stream do not depend on it.  Returns the previous setting. */
 int fqz5_set_host_decode(int mode);
 /* The host threads of the library's pools: this rank's share of the cores
  * (the affinity mask / $LOCAL_WORLD_SIZE, capped by $OMP_NUM_THREADS and 16;
@@ -172,6 +178,23 @@ void fqz5_trial_batch_stats(uint64_t *out3);
 /* Adaptive-model chains fqz5_decode_sections placed so far: out2[0] on host
  * cores, out2[1] on the GPU. */
 void fqz5_decode_chain_counts(uint64_t *out2);
+/* Plain rANS entropy chains the decoder calls placed so far: out2[0] on host
+ * cores, out2[1] on the GPU. */
+void fqz5_rans_chain_counts(uint64_t *out2);
+/* One rans_compress_4x16 stream whose order byte has only the order-1 and
+ * NOSZ bits set, decoded on the calling thread's host core (host_rans.cpp;
+ * no GPU): the bytes and the verdict of the GPU decoder.  out_cap is the
+ * size itself for a NOSZ stream.  0 with *out_size set, or -1 for a damaged
+ * stream and for any other order byte. */
+int fqz5_rans_dec_host(const unsigned char *in, size_t in_size, unsigned char *out,
+                       size_t out_cap, size_t *out_size);
+/* The chain placement of the cost model (host_dec.hpp plan) for `count`
+ * chains of n[i] symbols and kind[i] (0 sequence model, 1 fqz, 2 fqz with a
+ * sequence context, 3 rANS order-0, 4 rANS order-1) on `threads` host cores
+ * whose finish times before these chains are core_ns[threads] (NULL: idle):
+ * on_host[i] = 1 for a host core, 0 for the GPU. */
+void fqz5_host_plan(const uint64_t *n, const int *kind, int count, int threads,
+                    const double *core_ns, char *on_host);
 
 /* ---- CRC32 (zlib crc32, fqzcomp5.c:2268-2269, :2310-2311, :4443, :4670) --- */
 
