@@ -1183,14 +1183,16 @@ int fqz5_decode_sections(const fqz5_section *secs, int nsec, fqz5_section_result
             tn = std::thread([&] {
                 try {
                     FQZ5_HIP(hipSetDevice(gn->device));
-                    names_decode_batch(*gn, nd);
-                    // the names to their sections now, on the names context,
-                    // while the chains still run (after them, on the main
-                    // stream, -5 NovaSeq's 590 MB of names added ~50 ms)
-                    for (size_t k = 0; k < nd.size(); k++)
+                    // each block's names to their section as soon as that
+                    // block is rebuilt, on the names context, while the
+                    // chains (and the later blocks' rebuilds) still run (after
+                    // them, on the main stream, -5 NovaSeq's 590 MB of names
+                    // added ~50 ms)
+                    names_decode_batch(*gn, nd, [&](size_t k) {
                         if (nd[k].ok && nd[k].u_len)
                             FQZ5_HIP(hipMemcpyAsync(secs[who_name[k]].out, nd[k].names,
                                                     nd[k].u_len, hipMemcpyHostToDevice, gn->stream));
+                    });
                     gn->sync();                       // (nd's buffers are the sources)
                     if (trace) t_names_up = now_ms();
                 } catch (...) {

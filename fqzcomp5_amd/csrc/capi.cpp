@@ -22,6 +22,7 @@
 #include "arith_kernels.h"
 #include "fqz_codec.hpp"
 #include "host_dec.hpp"
+#include "host_lzp.hpp"
 
 // $FQZ5_SEGV_TRACE: on SIGSEGV print the native call stack (library offsets,
 // for llvm-symbolizer) before the default action (a diagnostic for faults in
@@ -698,6 +699,14 @@ int fqz5_host_threads(void) { return host::threads(); }
 
 void fqz5_trial_batch_stats(uint64_t *out3) {
     for (int i = 0; i < 3; i++) out3[i] = g_trial_stats[i].load();
+}
+
+int fqz5_unlzp_host(const unsigned char *in, size_t in_len, unsigned char *out, size_t out_cap,
+                     size_t *out_len) {
+    size_t n = 0;
+    const bool ok = host::unlzp(in, in_len, out, out_cap, &n);
+    if (out_len) *out_len = n;
+    return ok ? 0 : -1;
 }
 
 int fqz5_set_host_decode(int mode) {

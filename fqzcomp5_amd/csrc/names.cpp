@@ -1,10 +1,13 @@
 // names.cpp — fqzcomp5's name section (encode_names / decode_names,
 // fqzcomp5.c:1408-1794) over batches of candidates: the host splits and
 // tokenises (tok3.cpp), the GPU runs every lzp pass, every rANS stream (tok3
-// columns, lzp outputs, flag bytes) and every decode as one batch each.
+// columns, lzp outputs, flag bytes) and every decode as one batch each; the
+// decoder's unlzp of a name section runs on a host core (host_lzp.cpp) unless
+// host decoding is off.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -13,6 +16,7 @@
 #include <thread>
 
 #include "host_dec.hpp"
+#include "host_lzp.hpp"
 #include "names.hpp"
 #include "rans_format.hpp"
 
@@ -424,6 +428,7 @@ void name_dec_fetch(GpuCtx &g, NameDec &D, const std::vector<DecompressReq> &req
                     const std::vector<LzpDecReq> &lz) {
     D.fetched = false;
     D.ok = false;
+    D.host_lzp = false;
     D.names = D.fl = D.out2 = nullptr;
     D.fl_len = D.out2_len = 0;
     if (D.strat == 0) {
@@ -457,15 +462,71 @@ void name_dec_fetch(GpuCtx &g, NameDec &D, const std::vector<DecompressReq> &req
     D.fetched = true;
 }
 
+void name_dec_fetch_start(GpuCtx &g, NameDec &D, const std::vector<DecompressReq> &reqs) {
+    D.fetched = false;
+    D.ok = false;
+    D.host_lzp = true;
+    D.names = D.fl = D.out2 = D.lz_in = nullptr;
+    D.fl_len = D.out2_len = D.lz_in_len = 0;
+    // the lzp stream as the rANS stage left it: a host core expands it
+    // (name_dec_rebuild), so neither k_lzp_dec nor its table run for it
+    auto lzp_in = [&] {
+        if (D.req_main < 0 || !reqs[size_t(D.req_main)].ok) return false;
+        D.lz_in_len = reqs[size_t(D.req_main)].out_size;
+        D.lz_in = g.staging.alloc(size_t(D.lz_in_len) + 1);
+        g.download(D.lz_in, D.d_rout, D.lz_in_len);
+        return true;
+    };
+    if (D.strat == 0) {
+        if (!lzp_in()) return;
+        D.names = g.staging.alloc(size_t(D.u_len) + 1);
+        D.fetched = true;
+        return;
+    }
+    if (!tok3_dec_fetch_start(g, D.tok, reqs)) return;
+    if (D.strat == 2) {
+        if (D.req_flag < 0 || !reqs[size_t(D.req_flag)].ok) return;
+        if (D.clen2 && !lzp_in()) return;
+        D.fl_len = reqs[size_t(D.req_flag)].out_size;
+        D.fl = g.staging.alloc(size_t(D.fl_len) + 1);
+        g.download(D.fl, D.d_flag, D.fl_len);
+        if (D.clen2) D.out2 = g.staging.alloc(size_t(D.u_len) + 1);   // out = malloc(u_len) (:1659)
+        D.names = g.staging.alloc(size_t(D.u_len) + size_t(D.fl_len) * 2 + 1);
+    } else {
+        D.names = g.staging.alloc(size_t(D.u_len) + 1);
+    }
+    D.fetched = true;
+}
+
 void name_dec_rebuild(NameDec &D) {
     D.ok = false;
     if (!D.fetched) return;
+    D.ms_unlzp = D.ms_rebuild = 0;
+    // (name_dec_fetch_start) the lzp stream expands here, into `to`
+    auto unlzp = [&](uint8_t *to, size_t *n) {
+        const double t = now_ms();
+        const bool good = host::unlzp(D.lz_in, D.lz_in_len, to, D.u_len, n);
+        D.ms_unlzp = now_ms() - t;
+        return good;
+    };
     if (D.strat == 0) {
+        if (D.host_lzp) {
+            size_t n = 0;
+            if (!unlzp(D.names, &n)) return;
+            std::memset(D.names + n, 0, D.u_len - n);
+        }
         D.ok = true;
         return;
     }
+    const double tr = now_ms();
     std::vector<uint8_t> out1;
     if (!tok3_dec_rebuild(D.tok, out1)) return;
+    D.ms_rebuild = now_ms() - tr;
+    if (D.host_lzp && D.strat == 2 && D.clen2) {
+        size_t n = 0;
+        if (!unlzp(D.out2, &n)) return;
+        D.out2_len = uint32_t(n);
+    }
     if (D.strat == 1) {
         const size_t n = std::min<size_t>(out1.size(), D.u_len);
         std::memcpy(D.names, out1.data(), n);
@@ -516,8 +577,12 @@ void name_dec_finish(GpuCtx &g, NameDec &D, const std::vector<DecompressReq> &re
     name_dec_rebuild(D);
 }
 
-void names_decode_batch(GpuCtx &g, std::vector<NameDec> &jobs,
-                        const std::function<void()> &fetched) {
+namespace {
+// names_decode_batch with every lzp pass on the GPU (host_decode_mode() 0):
+// one k_lzp_dec launch for the batch, the blocks fetched one after another,
+// then rebuilt on the host threads
+void names_decode_batch_gpu(GpuCtx &g, std::vector<NameDec> &jobs,
+                            const std::function<void(size_t)> &block_done) {
     const double t0 = trace() ? now_ms() : 0;
     std::vector<DecompressReq> reqs;
     std::vector<char> good(jobs.size());
@@ -535,12 +600,114 @@ void names_decode_batch(GpuCtx &g, std::vector<NameDec> &jobs,
         if (good[k]) name_dec_fetch(g, jobs[k], reqs, lz);
         else jobs[k].fetched = false;
     const double t2 = trace() ? now_ms() : 0;
-    if (fetched) fetched();
     on_threads(jobs.size(), [&](size_t k) { name_dec_rebuild(jobs[k]); });
     if (trace())
         std::fprintf(stderr, "names decode: %zu sections, %zu rANS streams + lzp %.1f ms, "
                      "fetch %.1f ms, rebuild %.1f ms\n", jobs.size(), reqs.size(), t1 - t0,
                      t2 - t1, now_ms() - t2);
+    if (block_done)
+        for (size_t k = 0; k < jobs.size(); k++) block_done(k);
+}
+}  // namespace
+
+void names_decode_batch(GpuCtx &g, std::vector<NameDec> &jobs,
+                        const std::function<void(size_t)> &block_done) {
+    if (host_decode_mode() == 0) {
+        names_decode_batch_gpu(g, jobs, block_done);
+        return;
+    }
+    // Host decoding: after the rANS batch each block flows through on its
+    // own.  Its downloads (token streams, flags, the lzp stream as coded) are
+    // queued with one event behind them; a host task per block waits for the
+    // event, rebuilds the names and expands the lzp stream beside that
+    // (host_lzp.cpp), stitches, and hands the block to block_done on this
+    // thread while later blocks are still in flight.
+    const double t0 = now_ms();
+    std::vector<DecompressReq> reqs;
+    std::vector<char> good(jobs.size());
+    for (size_t k = 0; k < jobs.size(); k++) {
+        good[k] = name_dec_parse(jobs[k]);
+        if (good[k]) name_dec_add_requests(g, jobs[k], reqs);
+    }
+    if (!reqs.empty()) decompress_batch(g, reqs);
+    const double t1 = now_ms();
+    struct Events {                                  // one per block, destroyed on every exit
+        std::vector<hipEvent_t> ev;
+        ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    } evs;
+    evs.ev.assign(jobs.size(), nullptr);
+    std::mutex mu;
+    std::condition_variable cv;
+    std::vector<size_t> finished;                    // blocks whose host task has ended
+    std::exception_ptr err;
+    std::vector<double> t_fetch(jobs.size(), 0), t_done(jobs.size(), 0);
+    // (the staging arena is this thread's: every buffer is taken here, before
+    // the tasks start)
+    for (size_t k = 0; k < jobs.size(); k++) {
+        jobs[k].fetched = false;
+        if (!good[k]) continue;
+        name_dec_fetch_start(g, jobs[k], reqs);
+        FQZ5_HIP(hipEventCreateWithFlags(&evs.ev[k], hipEventDisableTiming));
+        FQZ5_HIP(hipEventRecord(evs.ev[k], g.stream));
+    }
+    host::Jobs tasks;                                // (joined before what it uses goes away)
+    tasks.start(jobs.size(), [&](size_t k) {
+        NameDec &D = jobs[k];
+        try {
+            if (D.fetched) {
+                FQZ5_HIP(hipEventSynchronize(evs.ev[k]));
+                t_fetch[k] = now_ms();
+                name_dec_rebuild(D);
+            }
+        } catch (...) {
+            D.ok = false;
+            std::lock_guard<std::mutex> lk(mu);
+            if (!err) err = std::current_exception();
+        }
+        t_done[k] = now_ms();
+        std::lock_guard<std::mutex> lk(mu);
+        finished.push_back(k);
+        cv.notify_one();
+    });
+    for (size_t seen = 0; seen < jobs.size();) {
+        std::vector<size_t> now;
+        {
+            std::unique_lock<std::mutex> lk(mu);
+            cv.wait(lk, [&] { return !finished.empty(); });
+            now.swap(finished);
+        }
+        seen += now.size();
+        if (block_done)
+            for (size_t k : now) block_done(k);
+    }
+    tasks.join();
+    if (err) std::rethrow_exception(err);
+    if (trace()) {
+        double f0 = 0, f1 = 0, d0 = 0, d1 = 0, ul = 0, rb = 0;
+        uint64_t lz_c = 0, lz_i = 0, lz_o = 0;           // the lzp streams: coded, as lzp, expanded
+        for (size_t k = 0; k < jobs.size(); k++) {
+            if (t_fetch[k]) {
+                f0 = f0 ? std::min(f0, t_fetch[k]) : t_fetch[k];
+                f1 = std::max(f1, t_fetch[k]);
+            }
+            d0 = d0 ? std::min(d0, t_done[k]) : t_done[k];
+            d1 = std::max(d1, t_done[k]);
+            ul = std::max(ul, jobs[k].ms_unlzp);
+            rb = std::max(rb, jobs[k].ms_rebuild);
+            if (jobs[k].ok && jobs[k].lz_in) {
+                lz_c += jobs[k].strat == 0 ? jobs[k].c_len : jobs[k].clen2;
+                lz_i += jobs[k].lz_in_len;
+                lz_o += jobs[k].strat == 0 ? jobs[k].u_len : jobs[k].out2_len;
+            }
+        }
+        std::fprintf(stderr, "names decode: %zu sections, %zu rANS streams %.1f ms; from the call's "
+                     "start: blocks fetched %.1f .. %.1f ms, complete %.1f .. %.1f ms (a host task "
+                     "per block: the longest unlzp %.1f ms, the longest rebuild %.1f ms; lzp streams "
+                     "%llu B coded, %llu B after rANS, %llu B expanded)\n",
+                     jobs.size(), reqs.size(), t1 - t0, f0 ? f0 - t0 : 0.0, f1 ? f1 - t0 : 0.0,
+                     d0 ? d0 - t0 : 0.0, d1 ? d1 - t0 : 0.0, ul, rb,
+                     (unsigned long long)lz_c, (unsigned long long)lz_i, (unsigned long long)lz_o);
+    }
 }
 
 }  // namespace fqz5

@@ -98,6 +98,13 @@ struct NameDec {
     bool fetched = false;            // name_dec_fetch: the device outputs on the host
     uint8_t *fl = nullptr, *out2 = nullptr;   // strat 2: flag bytes, comments
     uint32_t fl_len = 0, out2_len = 0;
+    // name_dec_fetch_start: the lzp stream (strat 0: of the names; strat 2: of
+    // the comments) as the rANS stage decoded it; name_dec_rebuild expands it
+    // on its host core
+    bool host_lzp = false;
+    uint8_t *lz_in = nullptr;
+    uint32_t lz_in_len = 0;
+    double ms_unlzp = 0, ms_rebuild = 0;   // (trace) name_dec_rebuild's unlzp / tok3 rebuild
 };
 
 // decode_names (fqzcomp5.c:1588-1794) in stages over a batch.
@@ -111,9 +118,17 @@ void name_dec_finish(GpuCtx &g, NameDec &D, const std::vector<DecompressReq> &re
                      const std::vector<LzpDecReq> &lz);
 void name_dec_fetch(GpuCtx &g, NameDec &D, const std::vector<DecompressReq> &reqs,
                     const std::vector<LzpDecReq> &lz);
+// name_dec_fetch for host decoding, without name_dec_add_lzp / lzp_decode_batch
+// before it: the block's downloads queued on g.stream and not waited for,
+// the lzp stream among them as the rANS stage left it.  name_dec_rebuild, once
+// g.stream has drained that far, expands it on the host (host_lzp.hpp).
+void name_dec_fetch_start(GpuCtx &g, NameDec &D, const std::vector<DecompressReq> &reqs);
 void name_dec_rebuild(NameDec &D);
-// fetched (optional) runs once the GPU work is done, before the host rebuild
+// block_done(k) (optional) runs on the calling thread once jobs[k] is complete
+// (ok or not).  With host decoding (host_decode_mode() != 0) that is while
+// later blocks are still being fetched and rebuilt, in the order they finish;
+// with mode 0 after the last one.
 void names_decode_batch(GpuCtx &g, std::vector<NameDec> &jobs,
-                        const std::function<void()> &fetched = {});
+                        const std::function<void(size_t)> &block_done = {});
 
 }  // namespace fqz5

@@ -920,23 +920,23 @@ void tok3_dec_add_requests(GpuCtx &g, Tok3Dec &D, const uint8_t *d_in,
     }
 }
 
-bool tok3_dec_fetch(GpuCtx &g, Tok3Dec &D, const std::vector<DecompressReq> &reqs) {
+bool tok3_dec_fetch_start(GpuCtx &g, Tok3Dec &D, const std::vector<DecompressReq> &reqs) {
     D.fetched = false;
     D.dec.assign(D.coded.size(), {});
-    std::vector<std::vector<uint8_t>> &dec = D.dec;
+    D.view.assign(D.coded.size(), {nullptr, 0});
     if (!D.use_arith) {
         for (size_t k = 0; k < D.coded.size(); k++) {
             const DecompressReq &r = reqs[D.req0 + k];
             if (!r.ok || r.out_size != D.coded[k].ulen) return false;
         }
         if (D.out_tot) {
+            // the streams stay where they land: the staging outlives the rebuild
             uint8_t *h = g.staging.alloc(D.out_tot);
             g.download(h, D.d_out, D.out_tot);
-            g.sync();
-            for (size_t k = 0; k < D.coded.size(); k++)
-                dec[k].assign(h + D.out_off[k], h + D.out_off[k] + D.coded[k].ulen);
+            for (size_t k = 0; k < D.coded.size(); k++) D.view[k] = {h + D.out_off[k], D.coded[k].ulen};
         }
     } else {
+        std::vector<std::vector<uint8_t>> &dec = D.dec;
         for (size_t k = 0; k < D.coded.size(); k++) {
             unsigned ol = D.coded[k].ulen;
             dec[k].resize(size_t(ol) + 1);
@@ -945,10 +945,17 @@ bool tok3_dec_fetch(GpuCtx &g, Tok3Dec &D, const std::vector<DecompressReq> &req
                 ol != D.coded[k].ulen)
                 return false;
             dec[k].resize(ol);
+            D.view[k] = {dec[k].data(), dec[k].size()};
         }
     }
     D.fetched = true;
     return true;
+}
+
+bool tok3_dec_fetch(GpuCtx &g, Tok3Dec &D, const std::vector<DecompressReq> &reqs) {
+    const bool ok = tok3_dec_fetch_start(g, D, reqs);
+    g.sync();
+    return ok;
 }
 
 bool tok3_dec_finish(GpuCtx &g, Tok3Dec &D, const std::vector<DecompressReq> &reqs,
@@ -958,26 +965,44 @@ bool tok3_dec_finish(GpuCtx &g, Tok3Dec &D, const std::vector<DecompressReq> &re
 
 bool tok3_dec_rebuild(Tok3Dec &D, std::vector<uint8_t> &out) {
     if (!D.fetched) return false;
-    struct Desc { std::vector<uint8_t> buf; size_t l = 0; bool have = false; };
+    // a stream: a view of its fetched bytes, or bytes made here (own)
+    struct Desc {
+        const uint8_t *p = nullptr;
+        size_t n = 0, l = 0;
+        bool have = false;
+        std::vector<uint8_t> own;
+    };
     std::vector<Desc> desc(MAX_TBLOCKS);
     const int nreads = D.nreads, max_tok = D.max_tok;
-    std::vector<std::vector<uint8_t>> &dec = D.dec;
     for (auto &e : D.order) {                          // in stream order, as the reference
         if (e.first == 2) {                            // an elided type stream: ty then MATCH
             Desc &c = desc[size_t(e.second & ~15)];
-            c.buf.assign(size_t(nreads), uint8_t(N_MATCH));
-            c.buf[0] = uint8_t(e.second & 15);
+            c.own.assign(size_t(nreads), uint8_t(N_MATCH));
+            c.own[0] = uint8_t(e.second & 15);
+            c.p = c.own.data();
+            c.n = c.own.size();
             c.have = true;
             c.l = 0;
         } else if (e.first == 1) {
             const auto &c = D.copies[size_t(e.second)];
             if (!desc[size_t(c.second)].have) return false;
-            desc[size_t(c.first)].buf = desc[size_t(c.second)].buf;
-            desc[size_t(c.first)].have = true;
-            desc[size_t(c.first)].l = 0;
+            const Desc &from = desc[size_t(c.second)];
+            Desc &to = desc[size_t(c.first)];
+            if (&to != &from) {
+                if (from.p == from.own.data() && from.n) {   // made here: its bytes may be remade
+                    to.own = from.own;
+                    to.p = to.own.data();
+                } else {
+                    to.p = from.p;
+                }
+                to.n = from.n;
+            }
+            to.have = true;
+            to.l = 0;
         } else {
             const Tok3Dec::Coded &c = D.coded[size_t(e.second)];
-            desc[size_t(c.i)].buf = std::move(dec[size_t(e.second)]);
+            desc[size_t(c.i)].p = D.view[size_t(e.second)].first;
+            desc[size_t(c.i)].n = D.view[size_t(e.second)].second;
             desc[size_t(c.i)].have = true;
             desc[size_t(c.i)].l = 0;
         }
@@ -986,21 +1011,21 @@ bool tok3_dec_rebuild(Tok3Dec &D, std::vector<uint8_t> &out) {
     // decode_name per name (:1023-1212)
     auto dtype = [&](int ntok) -> int {
         D_ &d = desc[size_t(ntok << 4)];
-        if (d.l >= d.buf.size()) return -1;
-        return d.buf[d.l++];
+        if (d.l >= d.n) return -1;
+        return d.p[d.l++];
     };
     auto dint = [&](int ntok, int ty, uint32_t *v) -> bool {
         D_ &d = desc[size_t(ntok << 4 | ty)];
-        if (d.l + 4 > d.buf.size()) return false;
-        const uint8_t *p = d.buf.data() + d.l;
+        if (d.l + 4 > d.n) return false;
+        const uint8_t *p = d.p + d.l;
         *v = uint32_t(p[0]) | uint32_t(p[1]) << 8 | uint32_t(p[2]) << 16 | uint32_t(p[3]) << 24;
         d.l += 4;
         return true;
     };
     auto dint1 = [&](int ntok, int ty, uint32_t *v) -> bool {
         D_ &d = desc[size_t(ntok << 4 | ty)];
-        if (d.l >= d.buf.size()) return false;
-        *v = d.buf[d.l++];
+        if (d.l >= d.n) return false;
+        *v = d.p[d.l++];
         return true;
     };
     auto fixed = [](char *cp, uint32_t v, uint8_t l) -> int {   // append_uint32_fixed (:233)
@@ -1072,14 +1097,14 @@ bool tok3_dec_rebuild(Tok3Dec &D, std::vector<uint8_t> &out) {
                     break;
                 case N_ALPHA: {
                     D_ &d = desc[size_t(ntok << 4 | N_ALPHA)];
-                    if (d.l >= d.buf.size()) { bad = true; break; }
+                    if (d.l >= d.n) { bad = true; break; }
                     int64_t l2 = 0;
                     char c;
                     const int64_t maxl = nlen - len;
                     do {
-                        c = char(d.buf[d.l++]);
+                        c = char(d.p[d.l++]);
                         nm[len + l2++] = c;
-                    } while (c && l2 < maxl && d.l < d.buf.size());
+                    } while (c && l2 < maxl && d.l < d.n);
                     T.type = N_ALPHA;
                     T.sval = int(len);
                     T.ival = int(l2 - 1);

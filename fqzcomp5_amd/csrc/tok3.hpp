@@ -81,7 +81,10 @@ struct Tok3Dec {
     uint8_t *d_out = nullptr;                                // the decoded streams, back to back
     std::vector<size_t> out_off;
     size_t out_tot = 0;
-    std::vector<std::vector<uint8_t>> dec;                   // tok3_dec_fetch: host copies
+    std::vector<std::vector<uint8_t>> dec;                   // tok3_dec_fetch: the arith streams
+    // tok3_dec_fetch: each coded stream on the host, in the fetching context's
+    // pinned staging (valid until that context's reset) or in `dec`
+    std::vector<std::pair<const uint8_t *, size_t>> view;
     bool fetched = false;
 };
 
@@ -97,6 +100,9 @@ void tok3_dec_add_requests(GpuCtx &g, Tok3Dec &D, const uint8_t *d_in,
 bool tok3_dec_finish(GpuCtx &g, Tok3Dec &D, const std::vector<DecompressReq> &reqs,
                      std::vector<uint8_t> &out);
 bool tok3_dec_fetch(GpuCtx &g, Tok3Dec &D, const std::vector<DecompressReq> &reqs);
+// tok3_dec_fetch without its wait: the download is queued on g.stream, and
+// the rebuild may start once that has drained
+bool tok3_dec_fetch_start(GpuCtx &g, Tok3Dec &D, const std::vector<DecompressReq> &reqs);
 bool tok3_dec_rebuild(Tok3Dec &D, std::vector<uint8_t> &out);
 
 // Host copies of device layouts: one gather on the device, one copy down.

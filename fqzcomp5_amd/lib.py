@@ -437,6 +437,24 @@ def unlzp(data: bytes, out_cap: int) -> bytes | None:
     return None if n < 0 else buf.raw[:n]
 
 
+def unlzp_host(data: bytes, out_cap: int) -> bytes | None:
+    """fqz5_unlzp_host: unlzp on a host core (no GPU); None where fqz5_unlzp
+    fails.  The buffer has out_cap bytes and a guard after them, which must
+    come back untouched."""
+    so = load()
+    so.fqz5_unlzp_host.restype = C.c_int
+    so.fqz5_unlzp_host.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                   C.POINTER(C.c_size_t)]
+    guard = b"\xa5" * 64
+    buf = C.create_string_buffer(out_cap + len(guard))
+    buf[out_cap:out_cap + len(guard)] = guard
+    n = C.c_size_t(0)
+    rc = so.fqz5_unlzp_host(bytes(data), len(data), buf, out_cap, C.byref(n))
+    if buf.raw[out_cap:out_cap + len(guard)] != guard or n.value > out_cap:
+        raise NativeError("fqz5_unlzp_host wrote past out_cap")
+    return None if rc else buf.raw[:n.value]
+
+
 def crc32(data: bytes, crc: int = 0) -> int:
     """zlib.crc32 computed on the GPU (fqz5_crc32, host buffer)."""
     return int(load().fqz5_crc32(crc, bytes(data), len(data)))

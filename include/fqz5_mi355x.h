@@ -188,6 +188,12 @@ void fqz5_rans_chain_counts(uint64_t *out2);
  * stream and for any other order byte. */
 int fqz5_rans_dec_host(const unsigned char *in, size_t in_size, unsigned char *out,
                        size_t out_cap, size_t *out_size);
+/* unlzp (lzp16e.c:166) on the calling thread's host core (host_lzp.cpp; no
+ * GPU): the bytes, length and verdict of fqz5_unlzp's kernel.  0 with
+ * *out_len set, or -1 when the stream would write past out_cap or ends
+ * inside a token (*out_len: the bytes written before that token). */
+int fqz5_unlzp_host(const unsigned char *in, size_t in_len, unsigned char *out, size_t out_cap,
+                    size_t *out_len);
 /* The chain placement of the cost model (host_dec.hpp plan) for `count`
  * chains of n[i] symbols and kind[i] (0 sequence model, 1 fqz, 2 fqz with a
  * sequence context, 3 rANS order-0, 4 rANS order-1) on `threads` host cores
