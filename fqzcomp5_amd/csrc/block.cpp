@@ -337,6 +337,7 @@ void fqz5_decode_chain_counts(uint64_t *out2) {
 }
 
 void fqz5_rans_chain_counts(uint64_t *out2) { rans_chain_counts(out2); }
+void fqz5_rans_enc_chain_counts(uint64_t *out2) { rans_enc_chain_counts(out2); }
 
 void fqz5_host_plan(const uint64_t *n, const int *kind, int count, int threads,
                     const double *core_ns, char *on_host) {

@@ -221,6 +221,18 @@ int host_decode_mode() {
     return v;
 }
 
+static std::atomic<int> g_host_enc{-1};
+int host_encode_mode() {
+    int v = g_host_enc.load();
+    if (v < 0) {
+        const char *e = std::getenv("FQZ5_HOST_ENCODE");
+        v = e ? std::atoi(e) : 2;
+        if (v < 0 || v > 3) v = 2;
+        g_host_enc.store(v);
+    }
+    return v;
+}
+
 // The calling thread's helper contexts: their own streams and arenas, for
 // work the thread hands to helper threads to run beside its own
 // (fqz5_sections_try: LZP3, fqz and sequence-model candidates beside the
@@ -712,6 +724,12 @@ int fqz5_unlzp_host(const unsigned char *in, size_t in_len, unsigned char *out, 
 int fqz5_set_host_decode(int mode) {
     const int prev = host_decode_mode();
     g_host_dec.store(mode < 0 || mode > 3 ? 2 : mode);
+    return prev;
+}
+
+int fqz5_set_host_encode(int mode) {
+    const int prev = host_encode_mode();
+    g_host_enc.store(mode < 0 || mode > 3 ? 2 : mode);
     return prev;
 }
 

@@ -530,6 +530,8 @@ bool hedge_chains();
 bool small_decoder_on();
 // the block decoder's adaptive-model chains on host cores (fqz5_set_host_decode)
 int host_decode_mode();
+// the encoder's bare rANS 4x16 chains on host cores (fqz5_set_host_encode)
+int host_encode_mode();
 // quality blocks decoded by the general (false) / small (true) fqz decoder
 uint64_t fqz_dec_blocks(bool small);
 int small_copies();   // hedged copies of a small-decoder block

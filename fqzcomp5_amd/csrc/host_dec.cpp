@@ -364,14 +364,22 @@ namespace {
 // 44.5 M-symbol sequence chains and 22 M-symbol packed qualities
 // (profiles/hostrans_step_trace.txt: 0.92-0.98 and 1.36-1.39)
 constexpr double HOST_RANS_O0_NS = 1.0, HOST_RANS_O1_NS = 1.4;
+// the encoder's bare chains (host_rans.cpp rans_enc_chain_o0 / _o1) on one core
+// of the same box, ns per symbol: tools/host_rans_enc_check --time over 44.5 M
+// symbols of the -3 bench's alphabets, alone and with 16 at once 0.64 and
+// 0.83-0.84 ("Encode long rANS chains on host cores")
+constexpr double HOST_RANS_ENC_O0_NS = 0.65, HOST_RANS_ENC_O1_NS = 0.85;
 // ns per symbol [kind][gpu]: priors from r04 on MI355X boxes (host: this
 // file's decoders on one core of the box, the -5 Illumina hybrid step; GPU:
 // k_fqz_dec_small 170-190, the general decoder with sequence contexts
 // 350-470, k_seq_dec 290-380).  The plain rANS 4x16 chains: GPU 54.4 ns a
 // step of 4 symbols for order-0 and 73.4 for order-1;
-// host: HOST_RANS_O0_NS / _O1_NS above
+// host: HOST_RANS_O0_NS / _O1_NS above.  The encoder's bare chains: GPU 18.3 ns
+// a step of 4 symbols for both orders (k_enc_chain2w);
+// host: HOST_RANS_ENC_O0_NS / _O1_NS above
 std::atomic<double> g_ns[CK_N][2] = {{{30.0}, {330.0}}, {{16.0}, {180.0}}, {{24.0}, {400.0}},
-                                     {{HOST_RANS_O0_NS}, {13.6}}, {{HOST_RANS_O1_NS}, {18.4}}};
+                                     {{HOST_RANS_O0_NS}, {13.6}}, {{HOST_RANS_O1_NS}, {18.4}},
+                                     {{HOST_RANS_ENC_O0_NS}, {4.6}}, {{HOST_RANS_ENC_O1_NS}, {4.6}}};
 }  // namespace
 
 double chain_ns(int kind, bool gpu) { return g_ns[kind][gpu ? 1 : 0].load(std::memory_order_relaxed); }

@@ -51,7 +51,10 @@ int cores_of_rank();
 // before these chains, i.e. what an earlier plan of the same call committed
 // (nullptr: `threads` idle cores); committed, when given, receives the cores'
 // finish times after them.
-enum ChainKind { CK_SEQ = 0, CK_FQZ = 1, CK_FQZ_SEQ = 2, CK_RANS_O0 = 3, CK_RANS_O1 = 4, CK_N };
+// CK_RANS_ENC_O0 / _O1: the encoder's bare NX = 4 chains (host_rans.hpp
+// rans_enc_chain_*), placed by Compressor::stage_encode (rans_compress.cpp).
+enum ChainKind { CK_SEQ = 0, CK_FQZ = 1, CK_FQZ_SEQ = 2, CK_RANS_O0 = 3, CK_RANS_O1 = 4,
+                 CK_RANS_ENC_O0 = 5, CK_RANS_ENC_O1 = 6, CK_N };
 double chain_ns(int kind, bool gpu);
 void chain_measured(int kind, bool gpu, double ns_per_symbol);
 std::vector<char> plan(const std::vector<uint64_t> &n, const std::vector<int> &kind, int threads,

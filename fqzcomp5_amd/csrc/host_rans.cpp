@@ -19,6 +19,7 @@
 // slot - start = 0, or = slot in the split layout.
 #include "host_rans.hpp"
 
+#include <cstdlib>
 #include <cstring>
 
 #include "rans_format.hpp"
@@ -298,8 +299,217 @@ int rans_dec_stream(const uint8_t *in, size_t in_size, uint8_t *out, size_t out_
     return 0;
 }
 
+// ---- the encoder's bare chains (rans_chain.hip chain_body_2w) ---------------
+// Chunk j holds the steps [256 j, 256 j + 256), the chunks run from the top
+// one (jtop = (T - 1) / 256) down, and checkpoint c = jtop - j holds the states
+// before chunk j: so checkpoint 0 is RANS_LOW and a checkpoint follows every
+// step k with k % 256 == 0, the last of them (k = 0) being the final states.
+// The steps the kernel pads a chunk or a short state with are identity steps
+// and are simply not made here.
+
+namespace {
+
+constexpr size_t ENC_CHUNK = 256;                // enc_chunk_steps(4)
+constexpr size_t O1_PAIR_MIN = 1u << 16;         // order-1 chains that build the 64 K pair table
+
+inline size_t enc_steps4(size_t n, bool o1) { return o1 ? n - 3 * (n / 4) : (n + 3) / 4; }
+
+// The encoder symbol as the host step reads it: the two fields of cmpl_sh
+// apart, the reciprocal's two shifts (32 and rcp_shift - 32) as one.
+struct HSym { uint32_t rcp, xmax, bias; uint16_t cmpl, sh; };
+inline HSym hsym(const EncSym &e) {
+    return {e.rcp, e.xmax, e.bias, uint16_t(e.cmpl_sh), uint16_t(32u + (e.cmpl_sh >> 16))};
+}
+
+// RansEncPutSymbol without its word.
+// The renormalisation must not become a branch (it is taken about every other
+// step: a mispredicting branch cost 2.4x).  clang keeps the select of the two
+// candidates a conditional move when told it is unpredictable (0.64 / 0.83 ns
+// per symbol for order 0 / 1 on the MI355X box's cores, against 0.81 / 1.19
+// for the shift below); gcc makes that select a branch, so it gets the shift
+// count from the comparison instead.
+inline uint32_t enc_step(uint32_t x, const HSym &e) {
+#if defined(__clang__)
+    const uint32_t xs = x >> 16;
+    const uint32_t xr = __builtin_unpredictable(x > e.xmax) ? xs : x;
+#else
+    const uint32_t xr = x >> (uint32_t(x > e.xmax) << 4);
+#endif
+    const uint32_t q = uint32_t((uint64_t(xr) * e.rcp) >> e.sh);
+    return q * e.cmpl + (xr + e.bias);
+}
+
+inline void enc_put(uint32_t *ck, size_t c, uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3) {
+    ck[4 * c] = x0;
+    ck[4 * c + 1] = x1;
+    ck[4 * c + 2] = x2;
+    ck[4 * c + 3] = x3;
+}
+
+}  // namespace
+
+size_t rans_enc_ck_words(size_t n, bool o1) {
+    const size_t T = enc_steps4(n, o1);
+    return ((T + ENC_CHUNK - 1) / ENC_CHUNK + 1) * 4;
+}
+
+void rans_enc_chain_o0(const EncSym *syms_in, const uint8_t *in, size_t n, uint32_t *ck) {
+    if (!n) return;
+    const size_t T = enc_steps4(n, false), jtop = (T - 1) / ENC_CHUNK;
+    HSym syms[256];
+    for (int s = 0; s < 256; s++) syms[s] = hsym(syms_in[s]);
+    uint32_t x0 = LOW, x1 = LOW, x2 = LOW, x3 = LOW;
+    enc_put(ck, 0, x0, x1, x2, x3);
+    size_t k = T;                                // steps left: [0, k)
+    if (n & 3) {                                 // the top step has n % 4 states
+        k--;
+        const uint8_t *p = in + 4 * k;
+        x0 = enc_step(x0, syms[p[0]]);
+        if ((n & 3) > 1) x1 = enc_step(x1, syms[p[1]]);
+        if ((n & 3) > 2) x2 = enc_step(x2, syms[p[2]]);
+        if (k % ENC_CHUNK == 0) enc_put(ck, jtop - k / ENC_CHUNK + 1, x0, x1, x2, x3);
+    }
+    while (k) {
+        const size_t lo = (k - 1) & ~(ENC_CHUNK - 1);
+        for (size_t t = k; t-- > lo;) {
+            const uint8_t *p = in + 4 * t;
+            x0 = enc_step(x0, syms[p[0]]);
+            x1 = enc_step(x1, syms[p[1]]);
+            x2 = enc_step(x2, syms[p[2]]);
+            x3 = enc_step(x3, syms[p[3]]);
+        }
+        enc_put(ck, jtop - lo / ENC_CHUNK + 1, x0, x1, x2, x3);
+        k = lo;
+    }
+}
+
+// `at(c, s)`: the symbol of byte s in the context of byte c
+template <class At>
+static void enc_chain_o1(const At &at, const uint8_t *in, size_t n, uint32_t *ck) {
+    const size_t isz = n / 4, T = enc_steps4(n, true), jtop = (T - 1) / ENC_CHUNK;
+    const uint8_t *p0 = in, *p1 = in + isz, *p2 = in + 2 * isz, *p3 = in + 3 * isz;
+    uint32_t x0 = LOW, x1 = LOW, x2 = LOW, x3 = LOW;
+    enc_put(ck, 0, x0, x1, x2, x3);
+    size_t k = T;
+    while (k) {
+        const size_t lo = (k - 1) & ~(ENC_CHUNK - 1);
+        size_t t = k;
+        // the tail: state 3 alone (its context is 0 at step 0: p3[-1] belongs to state 2)
+        for (; t > lo && t > isz; t--) x3 = enc_step(x3, at(t > 1 ? p3[t - 2] : 0, p3[t - 1]));
+        for (; t > lo && t > 1; t--) {                    // steps isz > t - 1 >= 1
+            const size_t s = t - 1;
+            x0 = enc_step(x0, at(p0[s - 1], p0[s]));
+            x1 = enc_step(x1, at(p1[s - 1], p1[s]));
+            x2 = enc_step(x2, at(p2[s - 1], p2[s]));
+            x3 = enc_step(x3, at(p3[s - 1], p3[s]));
+        }
+        if (t > lo) {                                     // step 0 of the quarters: context 0
+            x0 = enc_step(x0, at(0, p0[0]));
+            x1 = enc_step(x1, at(0, p1[0]));
+            x2 = enc_step(x2, at(0, p2[0]));
+            x3 = enc_step(x3, at(0, p3[0]));
+        }
+        enc_put(ck, jtop - lo / ENC_CHUNK + 1, x0, x1, x2, x3);
+        k = lo;
+    }
+}
+
+void rans_enc_chain_o1(const EncSym *tab, const uint8_t *remap, int A, const uint8_t *in, size_t n,
+                       uint32_t *ck) {
+    if (!n) return;
+    uint32_t row[256], col[256];                 // a byte as a context / as a symbol
+    for (int s = 0; s < 256; s++) {
+        col[s] = remap[s];
+        row[s] = uint32_t(remap[s]) * uint32_t(A);
+    }
+    if (n < O1_PAIR_MIN) {
+        std::vector<HSym> hs(size_t(A) * A);
+        for (size_t i = 0; i < hs.size(); i++) hs[i] = hsym(tab[i]);
+        const HSym *h = hs.data();
+        enc_chain_o1([&](uint32_t c, uint32_t s) -> const HSym & { return h[row[c] + col[s]]; }, in, n, ck);
+        return;
+    }
+    // a long chain: one table over the pair of bytes as they lie in the input
+    // (context | symbol << 8), so a step looks its symbol up with one load
+    std::vector<HSym> pair(65536);
+    for (uint32_t s = 0; s < 256; s++)
+        for (uint32_t c = 0; c < 256; c++) pair[c | s << 8] = hsym(tab[row[c] + col[s]]);
+    const HSym *h = pair.data();
+    enc_chain_o1([&](uint32_t c, uint32_t s) -> const HSym & { return h[c | s << 8]; }, in, n, ck);
+}
+
+void rans_enc_tab_o1(const uint16_t *f1, int A, int bits, EncSym *tab) {
+    for (int r = 0; r < A; r++) {
+        uint32_t start = 0;
+        for (int c = 0; c < A; c++) {
+            const uint32_t f = f1[size_t(r) * A + c];
+            tab[size_t(r) * A + c] = f ? make_encsym(start, f, bits) : EncSym{0, 0, 0, 0};
+            start += f;
+        }
+    }
+}
+
 }  // namespace host
 }  // namespace fqz5
+
+// freq: order-0 the 256 frequencies (sum 4096); order-1 256 x 256, row =
+// context byte, every row that occurs summing to 2^bits
+extern "C" uint32_t *fqz5_rans_enc_chain_host(const unsigned char *in, size_t n, int order, int bits,
+                                              const uint32_t *freq, size_t *ck_words) {
+    using namespace fqz5;
+    if (!in || !n || !freq || !ck_words || n > 0xffffffffu || (order != 0 && order != 1)) return nullptr;
+    if (order == 0 ? bits != 12 : (bits != 10 && bits != 12)) return nullptr;
+    const uint32_t M = 1u << bits;
+    std::vector<EncSym> tab;
+    uint8_t remap[256] = {0};
+    int A = 0;
+    if (order == 0) {
+        tab.assign(256, EncSym{0, 0, 0, 0});
+        uint32_t x = 0;
+        for (int s = 0; s < 256; s++) {
+            if (freq[s] > M - x) return nullptr;
+            if (freq[s]) tab[s] = make_encsym(x, freq[s], bits);
+            x += freq[s];
+        }
+        if (x != M) return nullptr;
+        for (size_t i = 0; i < n; i++)
+            if (!freq[in[i]]) return nullptr;
+    } else {
+        // the alphabet as the compressor makes it: 0 and every byte of the input
+        bool present[256] = {true};
+        for (size_t i = 0; i < n; i++) present[in[i]] = true;
+        for (int s = 0; s < 256; s++)
+            if (present[s]) remap[s] = uint8_t(A++);
+        std::vector<uint16_t> f1(size_t(A) * A, 0);
+        for (int r = 0; r < 256; r++) {
+            uint32_t x = 0;
+            for (int s = 0; s < 256; s++) {
+                const uint32_t f = freq[r * 256 + s];
+                if (!f) continue;
+                if (!present[r] || !present[s] || f > M - x) return nullptr;
+                f1[size_t(remap[r]) * A + remap[s]] = uint16_t(f);
+                x += f;
+            }
+            if (x && x != M) return nullptr;
+        }
+        // every (context, symbol) pair of the input needs a frequency
+        const size_t isz = n / 4;
+        for (size_t i = 0; i < n; i++) {
+            const bool first = i == 0 || (isz && i % isz == 0 && i / isz < 4);
+            const int c = first ? 0 : in[i - 1];
+            if (!f1[size_t(remap[c]) * A + remap[in[i]]]) return nullptr;
+        }
+        tab.resize(size_t(A) * A);
+        host::rans_enc_tab_o1(f1.data(), A, bits, tab.data());
+    }
+    const size_t words = host::rans_enc_ck_words(n, order == 1);
+    uint32_t *ck = static_cast<uint32_t *>(std::malloc(words * sizeof(uint32_t)));
+    if (!ck) return nullptr;
+    if (order == 0) host::rans_enc_chain_o0(tab.data(), in, n, ck);
+    else host::rans_enc_chain_o1(tab.data(), remap, A, in, n, ck);
+    *ck_words = words;
+    return ck;
+}
 
 extern "C" int fqz5_rans_dec_host(const unsigned char *in, size_t in_size, unsigned char *out,
                                   size_t out_cap, size_t *out_size) {

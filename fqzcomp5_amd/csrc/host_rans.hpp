@@ -5,13 +5,17 @@
 // interleaved states over 16-bit words.  One chain is serial whoever runs it;
 // a host core steps it several times faster than a GPU wave, and
 // Decompressor::run_djs (rans_decompress.cpp) places the long ones here by
-// the cost model of host_dec.hpp.  No HIP in this file or its .cpp.
+// the cost model of host_dec.hpp.  The encoder's bare chains (the states at
+// every chunk, no output words) follow below: Compressor::stage_encode
+// (rans_compress.cpp) places those the same way.  No HIP in this file or its
+// .cpp.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include <vector>
 
 namespace fqz5 {
+struct EncSym;   // rans_format.hpp
 namespace host {
 
 // The stream's frequency tables as the planner parses them
@@ -45,6 +49,28 @@ bool rans_dec_o1(const uint32_t *F, const uint8_t *alpha, size_t rows, int bits,
 // stream and for a damaged one.
 int rans_dec_stream(const uint8_t *in, size_t in_size, uint8_t *out, size_t out_cap,
                     size_t *out_size);
+
+// ---- the encoder's bare chains ---------------------------------------------
+// What k_enc_chain / k_enc_chain2w (rans_chain.hip) leave in EncJob::ck for an
+// NX = 4 job, bit for bit: the four states before every chunk of 256 steps,
+// from the top of the input down.  Words [0, 4) are RANS_LOW, the last four
+// the final states; k_enc_replay emits the stream's words from them.  The step
+// is chain_body_2w's: xr = x > xmax ? x >> 16 : x; q = mulhi(xr, rcp) >> sh;
+// x = q * cmpl + xr + bias, without a branch.
+//   Order-0: symbol i on state i & 3, ceil(n / 4) steps.
+//   Order-1: state z codes in[z * (n/4) + k] in the context in[z * (n/4) + k - 1]
+//   (0 at k = 0); state 3 also the tail, n - 3 * (n/4) steps in all.
+// Reads stay inside [in, in + n) and the table, writes inside
+// ck[0, rans_enc_ck_words(n, o1)).  n > 0.
+size_t rans_enc_ck_words(size_t n, bool o1);
+// syms: the 256 EncSym of the job (make_encsym over the normalised table)
+void rans_enc_chain_o0(const EncSym *syms, const uint8_t *in, size_t n, uint32_t *ck);
+// tab[A * A]: row = context, both by their index in the alphabet (remap)
+void rans_enc_chain_o1(const EncSym *tab, const uint8_t *remap, int A, const uint8_t *in, size_t n,
+                       uint32_t *ck);
+// k_enc_tab on the host: the A x A normalised frequencies f1 (a row sums to
+// 2^bits or 0) as encoder symbols, starts running in alphabet order
+void rans_enc_tab_o1(const uint16_t *f1, int A, int bits, EncSym *tab);
 
 }  // namespace host
 }  // namespace fqz5

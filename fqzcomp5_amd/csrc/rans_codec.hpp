@@ -100,5 +100,7 @@ void decompress_batch(GpuCtx &g, std::vector<DecompressReq> &reqs,
                       const host::CoreBudget *cores = nullptr);
 // entropy chains of stage B placed so far: out2[0] on host cores, out2[1] on the GPU
 void rans_chain_counts(uint64_t *out2);
+// the encoder's chains placed so far: out2[0] on host cores, out2[1] on the GPU
+void rans_enc_chain_counts(uint64_t *out2);
 
 }  // namespace fqz5

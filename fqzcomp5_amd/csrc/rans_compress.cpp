@@ -17,11 +17,15 @@
 // capacity failures (NULL returns) are decided in stage 6 from sizes: they
 // never change the bytes of a successful call.
 #include <sys/syscall.h>
+#include <time.h>
 #include <unistd.h>
 #include <algorithm>
 #include <map>
 #include <chrono>
 #include <climits>
+#include <condition_variable>
+#include <deque>
+#include <functional>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -32,6 +36,7 @@
 #include <thread>
 #include <vector>
 
+#include "host_rans.hpp"
 #include "kernels.h"
 #include "rans_codec.hpp"
 #include "rans_format.hpp"
@@ -105,6 +110,196 @@ struct StripeReq {
     uint32_t plen[256] = {0}, pidx[256] = {0};
     uint8_t *d_tr = nullptr;
     std::vector<std::vector<int>> leaves;   // per stripe, in candidate order
+};
+
+// ---- the chains that encode on host cores ------------------------------------
+// One bare NX = 4 chain is serial whoever runs it, and a host core steps it
+// several times faster than a wave (host_rans.hpp rans_enc_chain_*).
+// stage_encode places the chains by host_encode_mode(): a host-placed job's
+// input is copied to pinned memory, a pool thread runs its chain into pinned
+// checkpoints, and those are uploaded to the job's EncJob::ck, where the
+// replay passes find them as if k_enc_chain2w had left them.
+constexpr uint32_t HOST_CHAIN_MIN = 1u << 20;    // shorter chains are not worth a core (mode 2)
+std::atomic<uint64_t> g_enc_host{0}, g_enc_gpu{0};   // fqz5_rans_enc_chain_counts
+
+inline int enc_chain_kind(const EJ &j) { return j.o1 ? host::CK_RANS_ENC_O1 : host::CK_RANS_ENC_O0; }
+inline double thread_cpu_ns() {
+    timespec t;
+    if (clock_gettime(CLOCK_THREAD_CPUTIME_ID, &t)) return 0;
+    return double(t.tv_sec) * 1e9 + double(t.tv_nsec);
+}
+inline double now_ns() {
+    return std::chrono::duration<double, std::nano>(
+               std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// What every batch of the process shares (several compress_batch calls plan
+// and run at the same moment from the main, plain, stripe and names threads):
+// the host::threads() workers, the account of the host work the plans have
+// committed to them, the pinned buffers of the inputs and checkpoints, and the
+// stream of the input copies.  Never destroyed: it owns no context's memory,
+// so a context's reset() leaves it alone.
+class EncHost {
+  public:
+    static EncHost &get() {
+        static EncHost *p = new EncHost();
+        return *p;
+    }
+    // the tasks of one stage_encode call; wait() returns once all have run
+    struct Group {
+        std::mutex m;
+        std::condition_variable cv;
+        size_t left = 0;
+        bool failed = false;
+    };
+    void submit(Group &g, std::vector<std::function<void()>> tasks) {
+        {
+            std::lock_guard<std::mutex> lk(g.m);
+            g.left += tasks.size();
+        }
+        std::lock_guard<std::mutex> lk(m_);
+        const size_t want = size_t(host::threads());
+        while (workers_ < want) {
+            std::thread([this] { work(); }).detach();
+            workers_++;
+        }
+        for (auto &t : tasks) q_.push_back({&g, std::move(t)});
+        cv_.notify_all();
+    }
+    static void wait(Group &g) {
+        std::unique_lock<std::mutex> lk(g.m);
+        g.cv.wait(lk, [&] { return g.left == 0; });
+    }
+    // host::plan against the cores' committed finish times, which then
+    // include these chains
+    std::vector<char> plan(const std::vector<uint64_t> &n, const std::vector<int> &kind) {
+        std::lock_guard<std::mutex> lk(m_);
+        const double now = now_ns();
+        acct_.resize(size_t(host::threads()), 0.0);
+        std::vector<double> cores(acct_.size()), committed;
+        for (size_t i = 0; i < cores.size(); i++) cores[i] = std::max(0.0, acct_[i] - now);
+        std::vector<char> on = host::plan(n, kind, int(cores.size()), &cores, &committed);
+        for (size_t i = 0; i < committed.size() && i < acct_.size(); i++) acct_[i] = now + committed[i];
+        return on;
+    }
+    // A pinned buffer of at least n bytes, kept for the next step when given
+    // back (sizes in steps of a quarter of their power of two, so a step's
+    // buffers fit the next step's chains); nullptr when the
+    // budget ($FQZ5_HOST_ENC_PIN_GB, default 4) is spent.
+    uint8_t *take(size_t n, size_t *cls_out) {
+        size_t k = 20;
+        while ((size_t(2) << k) <= n) k++;
+        const size_t step = (size_t(1) << k) / 4, cls = (n + step - 1) / step * step;
+        *cls_out = cls;
+        {
+            std::lock_guard<std::mutex> lk(m_);
+            auto it = idle_.find(cls);
+            if (it != idle_.end() && !it->second.empty()) {
+                uint8_t *b = it->second.back();
+                it->second.pop_back();
+                return b;
+            }
+            static const size_t budget = [] {
+                const char *e = std::getenv("FQZ5_HOST_ENC_PIN_GB");
+                return size_t((e ? std::atof(e) : 4.0) * 1e9);
+            }();
+            if (held_ + cls > budget) return nullptr;
+            held_ += cls;
+        }
+        uint8_t *b = nullptr;
+        ChunkPool::alloc_calls().fetch_add(1, std::memory_order_relaxed);
+        if (hipHostMalloc(reinterpret_cast<void **>(&b), cls, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            std::lock_guard<std::mutex> lk(m_);
+            held_ -= cls;
+            return nullptr;
+        }
+        return b;
+    }
+    void give(uint8_t *b, size_t cls) {
+        std::lock_guard<std::mutex> lk(m_);
+        idle_[cls].push_back(b);
+    }
+    // the stream of the input copies: copies only, so none waits behind a kernel
+    hipStream_t copy_stream() {
+        std::lock_guard<std::mutex> lk(m_);
+        if (!copy_) FQZ5_HIP(hipStreamCreateWithFlags(&copy_, hipStreamNonBlocking));
+        return copy_;
+    }
+
+  private:
+    struct Task { Group *g; std::function<void()> fn; };
+    void work() {
+        for (;;) {
+            Task t;
+            {
+                std::unique_lock<std::mutex> lk(m_);
+                cv_.wait(lk, [&] { return !q_.empty(); });
+                t = std::move(q_.front());
+                q_.pop_front();
+            }
+            bool ok = true;
+            try { t.fn(); } catch (...) { ok = false; }
+            std::lock_guard<std::mutex> lk(t.g->m);
+            if (!ok) t.g->failed = true;
+            if (--t.g->left == 0) t.g->cv.notify_all();
+        }
+    }
+    std::mutex m_;
+    std::condition_variable cv_;
+    std::deque<Task> q_;
+    size_t workers_ = 0;
+    std::vector<double> acct_;                   // each core's committed finish time (steady clock, ns)
+    std::map<size_t, std::vector<uint8_t *>> idle_;
+    size_t held_ = 0;
+    hipStream_t copy_ = nullptr;
+};
+
+// One stage_encode call's host chains.  Its destructor waits for the tasks
+// and for the copies that use the buffers before it gives them back, so no
+// task and no copy outlives the call, whatever ends it.
+struct HostChains {
+    struct Chain {
+        int job;
+        const uint8_t *in;                       // pinned copy of the input (or the job's h_in)
+        hipEvent_t landed;                       // nullptr: nothing to wait for
+        uint32_t *ck;
+        size_t words;
+        double ns = 0, cpu_ns = 0, landed_ms = 0;   // the chain's wall and CPU time
+    };
+    GpuCtx &g;
+    EncHost::Group group;
+    std::vector<Chain> chains;
+    std::vector<std::pair<uint8_t *, size_t>> bufs;   // pool buffers and their classes
+    std::vector<hipEvent_t> events;
+    bool submitted = false;
+    explicit HostChains(GpuCtx &gc) : g(gc) {}
+    uint8_t *pinned(size_t n) {
+        if (n < (size_t(1) << 20)) return g.staging.alloc(n);
+        size_t cls = 0;
+        uint8_t *b = EncHost::get().take(n, &cls);
+        if (b) bufs.push_back({b, cls});
+        return b;
+    }
+    hipEvent_t event(unsigned flags) {
+        hipEvent_t e = nullptr;
+        FQZ5_HIP(hipEventCreateWithFlags(&e, flags));
+        events.push_back(e);
+        return e;
+    }
+    void join() {
+        if (submitted) EncHost::wait(group);
+        submitted = false;
+    }
+    ~HostChains() {
+        join();
+        if (!bufs.empty() || !events.empty()) {
+            for (hipEvent_t e : events) (void)hipEventSynchronize(e);
+            (void)hipStreamSynchronize(g.stream);
+        }
+        for (hipEvent_t e : events) (void)hipEventDestroy(e);
+        for (auto &b : bufs) EncHost::get().give(b.first, b.second);
+    }
 };
 
 // varint_put with the reference's end-of-buffer refusal (varint.h:173).
@@ -518,6 +713,16 @@ void Compressor::stage_encode() {
     };
     const double ta = trace ? now() : 0;
     const size_t nmain = jobs_.size();
+    // the chains on host cores (host_encode_mode(): 0 none, 1 every NX = 4
+    // chain, 2 by host::plan among those of 2^20 symbols and more, 3 every
+    // other one).  Their inputs exist once what the stream holds now has run.
+    const int hmode = host_encode_mode();
+    HostChains hc(g_);
+    hipEvent_t in_ready = nullptr;
+    if (hmode) {
+        in_ready = hc.event(hipEventDisableTiming);
+        FQZ5_HIP(hipEventRecord(in_ready, g_.stream));
+    }
     host_parallel(nmain, [&](size_t i) { if (!jobs_[i].o1) build_o0(jobs_[i]); });
     for (size_t i = 0; i < nmain; i++) {
         if (!jobs_[i].o1 || jobs_[i].table.size() <= 1000) continue;
@@ -534,6 +739,8 @@ void Compressor::stage_encode() {
     // LDS footprint (many waves per CU) and the rest.  Then the replay
     // passes over all chunks of all jobs (rans_chain.hip).
     std::vector<EncJob> ejs, ejb, eall;
+    int long_s = -1, long_b = -1;            // the longest chain of ejs / ejb
+    std::vector<uint32_t *> ck_of(jobs_.size(), nullptr);
     std::vector<uint32_t> items;
     uint32_t lds_s = 0, lds_b = 0, lds_r = 0;
     std::vector<int> order;
@@ -543,6 +750,103 @@ void Compressor::stage_encode() {
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
         return jobs_[a].n / jobs_[a].nx > jobs_[b].n / jobs_[b].nx;
     });
+    std::vector<char> on_host(jobs_.size(), 0);
+    double t_copy0 = 0;
+    if (hmode) {
+        std::vector<int> el;                     // eligible chains, longest first
+        for (int i : order)
+            if (jobs_[i].nx == 4 && (hmode != 2 || jobs_[i].n >= HOST_CHAIN_MIN)) el.push_back(i);
+        if (hmode == 2 && !el.empty()) {
+            std::vector<uint64_t> n;
+            std::vector<int> kind;
+            for (int i : el) { n.push_back(jobs_[i].n); kind.push_back(enc_chain_kind(jobs_[i])); }
+            const std::vector<char> on = EncHost::get().plan(n, kind);
+            for (size_t k = 0; k < el.size(); k++) on_host[el[k]] = on[k];
+        } else {
+            for (size_t k = 0; k < el.size(); k++) on_host[el[k]] = hmode == 1 || k % 2 == 0;
+        }
+        // pinned input (one per (d_in, n): RANS0 and RANS1 of a section share
+        // it) and checkpoints; a chain whose buffers the budget refuses stays
+        // on the GPU
+        std::map<std::pair<const uint8_t *, uint32_t>, uint8_t *> copies;
+        std::vector<std::pair<const uint8_t *, uint32_t>> copy_order;
+        for (int i : el) {
+            if (!on_host[i]) continue;
+            const EJ &j = jobs_[i];
+            const size_t words = host::rans_enc_ck_words(j.n, j.o1);
+            const uint8_t *in = j.h_in.empty() ? nullptr : j.h_in.data();
+            if (!in) {
+                const auto key = std::make_pair(j.d_in, j.n);
+                auto it = copies.find(key);
+                if (it == copies.end()) {
+                    it = copies.emplace(key, hc.pinned(j.n)).first;
+                    if (it->second) copy_order.push_back(key);
+                }
+                in = it->second;
+            }
+            uint32_t *ck = in ? reinterpret_cast<uint32_t *>(hc.pinned(words * 4)) : nullptr;
+            if (!ck) { on_host[i] = 0; continue; }
+            hc.chains.push_back({i, in, nullptr, ck, words});
+        }
+        // The copies, longest first, on the stream that only copies: issued
+        // before the chain launch below, they wait behind no kernel.  A long
+        // input has an event of its own, the short ones share the last.
+        if (!copy_order.empty()) {
+            FQZ5_HIP(hipEventSynchronize(in_ready));
+            hipStream_t cs = EncHost::get().copy_stream();
+            std::map<const uint8_t *, hipEvent_t> ev_of;
+            hipEvent_t shared = nullptr;
+            t_copy0 = now();
+            for (const auto &key : copy_order) {
+                uint8_t *dst = copies[key];
+                FQZ5_HIP(hipMemcpyAsync(dst, key.first, key.second, hipMemcpyDeviceToHost, cs));
+                if (key.second >= HOST_CHAIN_MIN) {
+                    ev_of[dst] = hc.event(hipEventDisableTiming);
+                    FQZ5_HIP(hipEventRecord(ev_of[dst], cs));
+                } else {
+                    if (!shared) shared = hc.event(hipEventDisableTiming);
+                    ev_of[dst] = shared;
+                }
+            }
+            if (shared) FQZ5_HIP(hipEventRecord(shared, cs));
+            for (auto &c : hc.chains) {
+                auto it = ev_of.find(c.in);
+                if (it != ev_of.end()) c.landed = it->second;
+            }
+        }
+        if (!hc.chains.empty()) {
+            // (the list is longest first: the workers take them in that order)
+            std::vector<std::function<void()>> tasks;
+            const int dev = g_.device;
+            for (size_t k = 0; k < hc.chains.size(); k++)
+                tasks.push_back([this, &hc, k, dev, &now] {
+                    HostChains::Chain &c = hc.chains[k];
+                    const EJ &j = jobs_[c.job];
+                    if (c.landed) {
+                        // (landed_ms only where the chain had to wait for its copy:
+                        // a later task finds it there and says nothing about it)
+                        (void)hipSetDevice(dev);
+                        if (hipEventQuery(c.landed) != hipSuccess) {
+                            (void)hipGetLastError();
+                            FQZ5_HIP(hipEventSynchronize(c.landed));
+                            c.landed_ms = now();
+                        }
+                    }
+                    const double a = now_ns(), ca = thread_cpu_ns();
+                    if (j.o1) {
+                        std::vector<EncSym> tab(j.f1.size());
+                        host::rans_enc_tab_o1(j.f1.data(), j.A, j.bits, tab.data());
+                        host::rans_enc_chain_o1(tab.data(), j.remap, j.A, c.in, j.n, c.ck);
+                    } else {
+                        host::rans_enc_chain_o0(j.syms.data(), c.in, j.n, c.ck);
+                    }
+                    c.ns = now_ns() - a;
+                    c.cpu_ns = thread_cpu_ns() - ca;
+                });
+            hc.submitted = true;
+            EncHost::get().submit(hc.group, std::move(tasks));
+        }
+    }
     uint32_t *d_lens = g_.arena.alloc_n<uint32_t>(jobs_.size());
     // every job's symbol table and O1 remap in one upload each (a stripe
     // candidate set is thousands of small jobs)
@@ -602,14 +906,19 @@ void Compressor::stage_encode() {
         const uint32_t nch = (steps + S - 1) / S;
         uint32_t *d_ck = g_.arena.alloc_n<uint32_t>(size_t(nch + 1) * uint32_t(j.nx));
         uint32_t *d_cnt = g_.arena.alloc_n<uint32_t>(nch);
+        ck_of[i] = d_ck;
         const EncJob e{j.d_in, d_tab, d_remap, j.d_end, d_lens + i, d_ck, d_cnt,
                        j.n, j.nx, j.bits, j.A, nch};
         // ejs: two-wave chains (NX=4, table in LDS: the long ones);
         // ejb: the rest (X32, O1 tables too big for LDS)
-        if (enc_chain_2w(j.o1, j.nx, uint32_t(j.A))) {
+        if (on_host[i]) {
+            // (its checkpoints come from a host core, below)
+        } else if (enc_chain_2w(j.o1, j.nx, uint32_t(j.A))) {
+            if (ejs.empty()) long_s = i;
             ejs.push_back(e);
             lds_s = std::max(lds_s, enc_2w_lds_bytes(j.o1, uint32_t(j.A)));
         } else {
+            if (ejb.empty()) long_b = i;
             ejb.push_back(e);
             lds_b = std::max(lds_b, enc_lds_bytes(j.o1, uint32_t(j.A)));
         }
@@ -627,26 +936,67 @@ void Compressor::stage_encode() {
     // per-kernel spans (fqz5_profile_read_all): their bytes once the
     // output lengths are known, below
     long tk_2w = -1, tk_1w = -1, tk_r0 = -1, tk_r1 = -1;
+    // a chain launch's time over its longest chain is the GPU's cost of that
+    // chain's kind (host::chain_measured, as the decoder's launches give it)
+    auto timed = [&](int longest) {
+        return hmode && longest >= 0 && jobs_[longest].nx == 4 && jobs_[longest].n >= HOST_CHAIN_MIN;
+    };
+    hipEvent_t ts[2] = {nullptr, nullptr}, tl[2] = {nullptr, nullptr};
+    if (timed(long_s)) { ts[0] = hc.event(hipEventDefault); ts[1] = hc.event(hipEventDefault); }
+    if (timed(long_b)) { tl[0] = hc.event(hipEventDefault); tl[1] = hc.event(hipEventDefault); }
+    const double t_launch = now();
     if (!ejs.empty()) {
         const EncJob *d = g_.upload(ejs);
         const EncJob *db = ejb.empty() ? nullptr : g_.upload(ejb);
         g_.fork();
         {
             ProfSpan sp(PK_ENC_CHAIN2W, g_.stream2);
+            if (ts[0]) FQZ5_HIP(hipEventRecord(ts[0], g_.stream2));
             FQZ5_HIP(launch_enc_chain2w(d, int(ejs.size()), lds_s, g_.stream2));
+            if (ts[1]) FQZ5_HIP(hipEventRecord(ts[1], g_.stream2));
             tk_2w = sp.end(0);
         }
         if (db) {
             ProfSpan sp(PK_ENC_CHAIN, g_.stream);
+            if (tl[0]) FQZ5_HIP(hipEventRecord(tl[0], g_.stream));
             FQZ5_HIP(launch_enc_chain(db, int(ejb.size()), lds_b, g_.stream));
+            if (tl[1]) FQZ5_HIP(hipEventRecord(tl[1], g_.stream));
             tk_1w = sp.end(0);
         }
         g_.join();
     } else if (!ejb.empty()) {
         const EncJob *db = g_.upload(ejb);
         ProfSpan sp(PK_ENC_CHAIN, g_.stream);
+        if (tl[0]) FQZ5_HIP(hipEventRecord(tl[0], g_.stream));
         FQZ5_HIP(launch_enc_chain(db, int(ejb.size()), lds_b, g_.stream));
+        if (tl[1]) FQZ5_HIP(hipEventRecord(tl[1], g_.stream));
         tk_1w = sp.end(0);
+    }
+    g_enc_gpu += ejs.size() + ejb.size();
+    g_enc_host += hc.chains.size();
+    // the host chains' checkpoints into their jobs' EncJob::ck, behind the
+    // GPU-placed chains in stream order and before the replay passes
+    double host_joined = 0, host_longest = 0, first_landed = 0, last_landed = 0;
+    if (!hc.chains.empty()) {
+        hc.join();
+        host_joined = now() - t_launch;
+        if (hc.group.failed) throw GpuError("rANS encode: a host chain failed");
+        for (const HostChains::Chain &c : hc.chains) {
+            const EJ &j = jobs_[c.job];
+            host_longest = std::max(host_longest, c.ns * 1e-6);
+            if (c.landed_ms > 0) {
+                first_landed = first_landed > 0 ? std::min(first_landed, c.landed_ms) : c.landed_ms;
+                last_landed = std::max(last_landed, c.landed_ms);
+            }
+            // The cost model gets the chain's CPU time: the plan shares the
+            // chains out over the cores itself, and the wall time of a chain
+            // that shared its core with the name tokenisers or a waiting
+            // helper thread (2-4x, from step to step) made the next plan leave
+            // long chains on the GPU, 205 ms each.
+            if (j.n >= HOST_CHAIN_MIN)
+                host::chain_measured(enc_chain_kind(j), false, (c.cpu_ns > 0 ? c.cpu_ns : c.ns) / double(j.n));
+            FQZ5_HIP(hipMemcpyAsync(ck_of[c.job], c.ck, c.words * 4, hipMemcpyHostToDevice, g_.stream));
+        }
     }
     if (!eall.empty()) {
         const EncJob *d_all = g_.upload(eall);
@@ -673,6 +1023,7 @@ void Compressor::stage_encode() {
         for (int i : order) {
             const double b = double(jobs_[i].n) + lens[i];
             bytes += b;
+            if (on_host[i]) continue;
             (enc_chain_2w(jobs_[i].o1, jobs_[i].nx, uint32_t(jobs_[i].A)) ? b2w : b1w) += b;
         }
         prof_bytes(tk_2w, b2w);
@@ -685,14 +1036,32 @@ void Compressor::stage_encode() {
             g_.prof.enc_bytes += bytes;
         }
     }
+    auto gpu_measured = [&](hipEvent_t *e, int longest) {
+        float ms = 0;
+        if (e[0] && hipEventElapsedTime(&ms, e[0], e[1]) == hipSuccess)
+            host::chain_measured(enc_chain_kind(jobs_[longest]), true, double(ms) * 1e6 / double(jobs_[longest].n));
+    };
+    gpu_measured(ts, long_s);
+    gpu_measured(tl, long_b);
     for (size_t i = 0; i < jobs_.size(); i++) jobs_[i].payload = jobs_[i].n ? lens[i] : 0;
     for (size_t i = nmain; i < jobs_.size(); i++) finish_job(jobs_[i]);
     for (size_t i = 0; i < nmain; i++) finish_job(jobs_[i]);
-    if (trace)
+    if (trace) {
         std::fprintf(stderr, "[tid %ld] encode: tables %.1f ms (%zu syms), uploads+launch %.1f ms, "
-                     "wait %.1f ms, finish %.1f ms\n", long(syscall(SYS_gettid)), tb - ta, nsyms + all_syms.size(), tc - tb,
+                     "wait %.1f ms, finish %.1f ms", long(syscall(SYS_gettid)), tb - ta, nsyms + all_syms.size(), tc - tb,
                      td - tc, now() - td);
+        if (hmode)
+            std::fprintf(stderr, "; host chains %zu of %zu (longest %.1f ms, joined %.1f ms after the launch, "
+                         "chains waited for input copies that landed %.1f .. %.1f ms after the first was issued), ns per symbol "
+                         "o0 host %.2f gpu %.2f, o1 host %.2f gpu %.2f",
+                         hc.chains.size(), hc.chains.size() + ejs.size() + ejb.size(), host_longest, host_joined,
+                         first_landed > 0 ? first_landed - t_copy0 : 0.0, last_landed > 0 ? last_landed - t_copy0 : 0.0,
+                         host::chain_ns(host::CK_RANS_ENC_O0, false), host::chain_ns(host::CK_RANS_ENC_O0, true),
+                         host::chain_ns(host::CK_RANS_ENC_O1, false), host::chain_ns(host::CK_RANS_ENC_O1, true));
+        std::fprintf(stderr, "\n");
+    }
 }
+
 
 void Compressor::finish_job(EJ &j) {
     j.layout.clear();
@@ -960,6 +1329,11 @@ void Compressor::run(std::vector<CompressReq> &reqs) {
 }
 
 }  // namespace
+
+void rans_enc_chain_counts(uint64_t *out2) {
+    out2[0] = g_enc_host.load();
+    out2[1] = g_enc_gpu.load();
+}
 
 void compress_batch(GpuCtx &g, std::vector<CompressReq> &reqs) {
     static const bool trace = std::getenv("FQZ5_STEP_TRACE") != nullptr;

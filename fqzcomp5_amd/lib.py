@@ -237,6 +237,44 @@ def rans_chain_counts() -> tuple[int, int]:
     return int(c[0]), int(c[1])
 
 
+def set_host_encode(mode: int) -> int:
+    """fqz5_set_host_encode: where the compressor runs its bare NX = 4 chains
+    (0 GPU, 1 host, 2 by cost, 3 every other one); the previous mode."""
+    so = load()
+    so.fqz5_set_host_encode.restype = C.c_int
+    so.fqz5_set_host_encode.argtypes = [C.c_int]
+    return int(so.fqz5_set_host_encode(mode))
+
+
+def rans_enc_chain_counts() -> tuple[int, int]:
+    """Encoder chains placed so far: (on host cores, on the GPU)."""
+    c = (C.c_uint64 * 2)()
+    so = load()
+    so.fqz5_rans_enc_chain_counts.restype = None
+    so.fqz5_rans_enc_chain_counts.argtypes = [C.POINTER(C.c_uint64)]
+    so.fqz5_rans_enc_chain_counts(c)
+    return int(c[0]), int(c[1])
+
+
+def rans_enc_chain_host(data: bytes, order: int, bits: int, freq) -> list[int] | None:
+    """fqz5_rans_enc_chain_host: the bare encoder chain's checkpoints (u32
+    words) on a host core (no GPU).  freq: 256 frequencies (order 0) or
+    256 x 256, row = context byte (order 1), flat; None where it refuses."""
+    want = 256 if order == 0 else 65536
+    fa = (C.c_uint32 * want)(*[int(x) for x in freq])
+    n = C.c_size_t(0)
+    so = load()
+    so.fqz5_rans_enc_chain_host.restype = C.c_void_p
+    so.fqz5_rans_enc_chain_host.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int,
+                                            C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)]
+    p = so.fqz5_rans_enc_chain_host(bytes(data), len(data), order, bits, fa, C.byref(n))
+    if not p:
+        return None
+    out = list((C.c_uint32 * n.value).from_address(p))
+    _libc.free(p)
+    return out
+
+
 def rans_dec_host(comp: bytes, cap: int) -> bytes | None:
     """fqz5_rans_dec_host: a plain order-0 / order-1 4x16 stream on a host
     core (no GPU); None where it fails or refuses the order byte."""

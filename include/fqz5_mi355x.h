@@ -194,9 +194,33 @@ int fqz5_rans_dec_host(const unsigned char *in, size_t in_size, unsigned char *o
  * inside a token (*out_len: the bytes written before that token). */
 int fqz5_unlzp_host(const unsigned char *in, size_t in_len, unsigned char *out, size_t out_cap,
                     size_t *out_len);
+/* Where the rANS compressor runs its bare NX = 4 encoder chains (order-0 and
+ * order-1, any alphabet; rans_compress_*, the block encoder's rANS candidates
+ * and names): 0 = k_enc_chain / k_enc_chain2w on the GPU, 1 = every such chain
+ * on host cores (host_rans.cpp), 2 = by cost among the chains of 2^20 symbols
+ * and more, against the host work every concurrent batch has already committed
+ * (the default; $FQZ5_HOST_ENCODE overrides it), 3 = every other one.  A
+ * host-placed chain leaves the checkpoints the kernel would have left, and the
+ * replay kernels emit the stream from them: the output bytes do not depend on
+ * the setting.  32-state (X32) chains always run on the GPU.  Returns the
+ * previous setting. */
+int fqz5_set_host_encode(int mode);
+/* Encoder chains placed so far: out2[0] on host cores, out2[1] on the GPU. */
+void fqz5_rans_enc_chain_counts(uint64_t *out2);
+/* The bare encoder chain of `in` (n > 0 bytes) on the calling thread's host
+ * core (no GPU): the checkpoints k_enc_chain / k_enc_chain2w leave in
+ * EncJob::ck for the same job, (ceil(steps / 256) + 1) * 4 words of which the
+ * first four are the initial and the last four the final states.  order 0:
+ * bits = 12 and freq[256] sums to 4096.  order 1: bits = 10 or 12 and
+ * freq[256 * 256] holds one row per context byte, every row that occurs
+ * summing to 2^bits.  Returns a malloc'd array with *ck_words set, or NULL
+ * (bad arguments, or a byte or pair of the input without a frequency). */
+uint32_t *fqz5_rans_enc_chain_host(const unsigned char *in, size_t n, int order, int bits,
+                                   const uint32_t *freq, size_t *ck_words);
 /* The chain placement of the cost model (host_dec.hpp plan) for `count`
  * chains of n[i] symbols and kind[i] (0 sequence model, 1 fqz, 2 fqz with a
- * sequence context, 3 rANS order-0, 4 rANS order-1) on `threads` host cores
+ * sequence context, 3 rANS order-0, 4 rANS order-1, 5 / 6 the encoder's bare
+ * rANS order-0 / order-1 chain) on `threads` host cores
  * whose finish times before these chains are core_ns[threads] (NULL: idle):
  * on_host[i] = 1 for a host core, 0 for the GPU. */
 void fqz5_host_plan(const uint64_t *n, const int *kind, int count, int threads,
