@@ -11,7 +11,6 @@
 // trial state machine is replayed on the host in block order, which gives
 // exactly the choices of a single-threaded (-t1) reference run.
 #include <atomic>
-#include <chrono>
 #include <cstdio>
 #include <algorithm>
 #include <cstdlib>
@@ -339,16 +338,6 @@ void fqz5_decode_chain_counts(uint64_t *out2) {
 void fqz5_rans_chain_counts(uint64_t *out2) { rans_chain_counts(out2); }
 void fqz5_rans_enc_chain_counts(uint64_t *out2) { rans_enc_chain_counts(out2); }
 
-void fqz5_host_plan(const uint64_t *n, const int *kind, int count, int threads,
-                    const double *core_ns, char *on_host) {
-    const std::vector<uint64_t> nv(n, n + count);
-    const std::vector<int> kv(kind, kind + count);
-    std::vector<double> cores;
-    if (core_ns) cores.assign(core_ns, core_ns + threads);
-    const std::vector<char> on = host::plan(nv, kv, threads, core_ns ? &cores : nullptr);
-    std::copy(on.begin(), on.end(), on_host);
-}
-
 void fqz5_trial_counts(uint64_t *out2) {
     out2[0] = g_fqz_tried.load();
     out2[1] = g_fqz_pruned.load();
@@ -377,14 +366,9 @@ void fqz5_trial_schedule(const int32_t *sec_ids, int nsec, const uint32_t *avail
     }
 }
 
-static bool step_trace() {
-    static const bool on = std::getenv("FQZ5_STEP_TRACE") != nullptr;
-    return on;
-}
-static double now_ms() {
-    return std::chrono::duration<double, std::milli>(
-               std::chrono::steady_clock::now().time_since_epoch()).count();
-}
+using host::now_ms;
+using host::now_ns;
+using host::step_trace;
 
 int fqz5_sections_try(const fqz5_section *secs, int nsec, const uint32_t *masks,
                       uint32_t *sizes) {
@@ -964,8 +948,8 @@ int fqz5_decode_sections(const fqz5_section *secs, int nsec, fqz5_section_result
     } exit_trace{step_trace() ? now_ms() : 0.0};
     try {
         GpuCtx &g = gpu();
-        static const bool trace = std::getenv("FQZ5_STEP_TRACE") != nullptr;
-        const auto t0 = std::chrono::steady_clock::now();
+        const bool trace = step_trace();
+        const double t0 = now_ms();
         // section headers to the host, then the rANS payloads
         size_t tot = 0;
         for (int i = 0; i < nsec; i++) tot += secs[i].in_size;
@@ -1074,10 +1058,10 @@ int fqz5_decode_sections(const fqz5_section *secs, int nsec, fqz5_section_result
             reqs.push_back(r);
             who.push_back(i);
         }
-        const auto t1 = std::chrono::steady_clock::now();
-        // ---- where each adaptive-model chain decodes (host_decode_mode():
-        // 0 the GPU, 1 host cores, 2 by the chains' measured costs,
-        // host::plan).  A quality chain with a sequence context waits for
+        const double t1 = now_ms();
+        // ---- where each adaptive-model chain decodes (host::place by
+        // host_decode_mode(): the sequence chains, then the quality chains, of
+        // any length).  A quality chain with a sequence context waits for
         // its block's bases; when those come from a host chain it runs on
         // the host too (its bases are there) ----------------------------------
         const int hmode = host_decode_mode();
@@ -1092,20 +1076,13 @@ int fqz5_decode_sections(const fqz5_section *secs, int nsec, fqz5_section_result
                     if (seqd[m].d_out == f.d_seq) fqz_src[k] = int(m);
             }
         }
-        std::vector<char> seq_on_host(seqd.size(), hmode == 1), fqz_on_host(fqz.size(), hmode == 1);
-        if (hmode == 3) {                 // (tests: every other chain on the host)
-            for (size_t m = 0; m < seqd.size(); m++) seq_on_host[m] = m % 2 == 0;
-            for (size_t k = 0; k < fqz.size(); k++) fqz_on_host[k] = (seqd.size() + k) % 2 == 0;
-        }
-        if (hmode == 2 && !(seqd.empty() && fqz.empty())) {
-            std::vector<uint64_t> n;
-            std::vector<int> kind;
-            for (const SeqDecReq &q : seqd) { n.push_back(q.n); kind.push_back(host::CK_SEQ); }
-            for (size_t k = 0; k < fqz.size(); k++) { n.push_back(fqz[k].out_cap); kind.push_back(fqz_kind[k]); }
-            const std::vector<char> on = host::plan(n, kind, host::threads());
-            for (size_t m = 0; m < seqd.size(); m++) seq_on_host[m] = on[m];
-            for (size_t k = 0; k < fqz.size(); k++) fqz_on_host[k] = on[seqd.size() + k];
-        }
+        std::vector<uint64_t> chain_n;
+        std::vector<int> chain_kind;
+        for (const SeqDecReq &q : seqd) { chain_n.push_back(q.n); chain_kind.push_back(host::CK_SEQ); }
+        for (size_t k = 0; k < fqz.size(); k++) { chain_n.push_back(fqz[k].out_cap); chain_kind.push_back(fqz_kind[k]); }
+        const std::vector<char> on = host::place(hmode, chain_n, chain_kind, 0);
+        std::vector<char> seq_on_host(on.begin(), on.begin() + seqd.size()),
+                          fqz_on_host(on.begin() + seqd.size(), on.end());
         for (size_t k = 0; k < fqz.size(); k++)
             if (fqz_src[k] >= 0 && seq_on_host[size_t(fqz_src[k])]) fqz_on_host[k] = 1;
         g_chains_host += uint64_t(std::count(seq_on_host.begin(), seq_on_host.end(), 1) +
@@ -1139,11 +1116,12 @@ int fqz5_decode_sections(const fqz5_section *secs, int nsec, fqz5_section_result
             hc_idx.push_back(k);
             hc_kind.push_back(fqz_kind[k]);
         }
-        auto timed = [](int kind, size_t n, const std::function<bool()> &fn) {
-            const auto a = std::chrono::steady_clock::now();
+        // fn() under the clock, for the cost model: a host chain of n symbols
+        // that decoded, or (gpu) a GPU batch whose longest chain has n
+        auto timed = [](int kind, bool gpu, uint64_t n, const std::function<bool()> &fn) {
+            const double a = now_ns();
             const bool ok = fn();
-            const double ns = std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - a).count();
-            if (ok && n >= (1u << 20)) host::chain_measured(kind, false, ns / double(n));
+            if (ok) host::measured(kind, gpu, n, now_ns() - a);
             return ok;
         };
         host::Jobs hjobs;
@@ -1155,13 +1133,13 @@ int fqz5_decode_sections(const fqz5_section *secs, int nsec, fqz5_section_result
             HostChain &c = hc[j];
             if (hc_kind[j] == host::CK_SEQ) {
                 const SeqDecReq &q = seqd[hc_idx[j]];
-                c.ok = timed(host::CK_SEQ, q.n, [&] {
+                c.ok = timed(host::CK_SEQ, false, q.n, [&] {
                     return host::seq_decode(seq_h[hc_idx[j]], q.in_size, q.lens, q.nrec, q.both, q.k,
                                             c.buf, q.n) == 0;
                 });
             } else {
                 const FqzDecReq &f = fqz[hc_idx[j]];
-                c.ok = timed(host::CK_FQZ, c.cap, [&] {
+                c.ok = timed(host::CK_FQZ, false, c.cap, [&] {
                     return host::fqz_decode(f.h_in, f.in_size, c.buf, c.cap, &c.n, nullptr, 0, nullptr, 0) == 0;
                 });
             }
@@ -1205,13 +1183,6 @@ int fqz5_decode_sections(const fqz5_section *secs, int nsec, fqz5_section_result
             std::thread &t;
             ~Join() { if (t.joinable()) t.join(); }
         } join_names{tn};
-        // a GPU batch's time over its longest chain: the chain cost the plan reads
-        auto gpu_timed = [](int kind, uint64_t longest, const std::function<void()> &fn) {
-            const auto a = std::chrono::steady_clock::now();
-            fn();
-            const double ns = std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - a).count();
-            if (longest >= (1u << 20)) host::chain_measured(kind, true, ns / double(longest));
-        };
         // GPU quality sections without a sequence context need nothing else
         // of this call: they decode on the fqz helper context from a thread
         // of their own, beside the rANS / LZP / sequence-model work, instead
@@ -1236,7 +1207,7 @@ int fqz5_decode_sections(const fqz5_section *secs, int nsec, fqz5_section_result
             tf = std::thread([&] {
                 try {
                     FQZ5_HIP(hipSetDevice(gf->device));
-                    gpu_timed(host::CK_FQZ, early_longest, [&] { fqz_decode_batch(*gf, fqz_early); });
+                    timed(host::CK_FQZ, true, early_longest, [&] { fqz_decode_batch(*gf, fqz_early); return true; });
                 } catch (...) {
                     ferr = std::current_exception();
                 }
@@ -1261,7 +1232,7 @@ int fqz5_decode_sections(const fqz5_section *secs, int nsec, fqz5_section_result
             ts = std::thread([&] {
                 try {
                     FQZ5_HIP(hipSetDevice(gs->device));
-                    gpu_timed(host::CK_SEQ, seq_longest, [&] { seq_decode_batch(*gs, seq_gpu); });
+                    timed(host::CK_SEQ, true, seq_longest, [&] { seq_decode_batch(*gs, seq_gpu); return true; });
                 } catch (...) {
                     serr = std::current_exception();
                 }
@@ -1278,8 +1249,7 @@ int fqz5_decode_sections(const fqz5_section *secs, int nsec, fqz5_section_result
         const double t_rans = trace ? now_ms() : 0;
         if (trace)
             std::fprintf(stderr, "decode_sections: %zu bytes to host in %.1f ms, rANS %.1f ms\n", tot,
-                         std::chrono::duration<double, std::milli>(t1 - t0).count(),
-                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count());
+                         t1 - t0, now_ms() - t1);
         if (!lzd.empty()) {
             std::vector<LzpDecReq> run;
             std::vector<int> run_who;
@@ -1314,7 +1284,7 @@ int fqz5_decode_sections(const fqz5_section *secs, int nsec, fqz5_section_result
                     longest = std::max<uint64_t>(longest, fqz[k].out_cap);
                 }
             if (!late.empty()) {
-                gpu_timed(host::CK_FQZ_SEQ, longest, [&] { fqz_decode_batch(g, late); });
+                timed(host::CK_FQZ_SEQ, true, longest, [&] { fqz_decode_batch(g, late); return true; });
                 for (size_t k = 0; k < late.size(); k++) fqz[late_of[k]] = late[k];
             }
         }
@@ -1360,7 +1330,7 @@ int fqz5_decode_sections(const fqz5_section *secs, int nsec, fqz5_section_result
             hb.start(late.size(), [&](size_t t) {
                 HostChain &c = hc[late[t]];
                 const FqzDecReq &f = fqz[hc_idx[late[t]]];
-                c.ok = timed(host::CK_FQZ_SEQ, c.cap, [&] {
+                c.ok = timed(host::CK_FQZ_SEQ, false, c.cap, [&] {
                     return host::fqz_decode(f.h_in, f.in_size, c.buf, c.cap, &c.n, nullptr, 0,
                                             recp[late[t]].data(), f.nrec) == 0;
                 });
@@ -1408,10 +1378,9 @@ int fqz5_decode_sections(const fqz5_section *secs, int nsec, fqz5_section_result
         if (gf) gf->reset();
         if (gs) gs->reset();
         if (trace) {
-            const double tb = std::chrono::duration<double, std::milli>(t0.time_since_epoch()).count();
             std::fprintf(stderr, "decode_sections: from its start: rANS done %.1f, host chains joined "
-                         "%.1f, names uploaded %.1f, names joined %.1f, reset %.1f ms\n", t_rans - tb,
-                         t_hc - tb, t_names_up ? t_names_up - tb : -1.0, t_nj - tb, now_ms() - tb);
+                         "%.1f, names uploaded %.1f, names joined %.1f, reset %.1f ms\n", t_rans - t0,
+                         t_hc - t0, t_names_up ? t_names_up - t0 : -1.0, t_nj - t0, now_ms() - t0);
         }
         return 0;
     } catch (const std::exception &e) {

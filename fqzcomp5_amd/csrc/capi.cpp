@@ -21,7 +21,7 @@
 #include "fqz_kernels.h"
 #include "arith_kernels.h"
 #include "fqz_codec.hpp"
-#include "host_dec.hpp"
+#include "host_sched.hpp"
 #include "host_lzp.hpp"
 
 // $FQZ5_SEGV_TRACE: on SIGSEGV print the native call stack (library offsets,

@@ -10,20 +10,16 @@
 // these chains here, on a pool of host threads beside the GPU's rANS and name
 // work, when the host mode asks for it (fqz5_set_host_decode).  Same inputs,
 // same bytes as the GPU decoders (tests/test_host_dec.py checks both against
-// the reference's vectors).  The placement plan at the end of this file
-// (plan, chain_ns, chain_measured) also serves the plain rANS 4x16 chains of
-// host_rans.cpp, which rans_decompress.cpp places the same way.
+// the reference's vectors).  Where a chain runs is host_sched.hpp's decision.
 //
 // Models (own layout, reference arithmetic): an adaptive list per context
 // (c_simple_model.h: freq +16, halved past 65519, one bubble step per
 // update) stored as parallel u16 frequency / u8 symbol arrays; the 4- and
 // 2-symbol sequence models (c_small_model.h: +1, halved at a total of 255)
 // as four u8 counts.
-#include <sched.h>
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
-#include <atomic>
 #include <cstring>
 #include <vector>
 
@@ -356,104 +352,6 @@ int seq_decode(const uint8_t *in, uint32_t in_size, const uint32_t *lens, int nr
         else state = ns ? 1 : 0;
     }
     return 0;
-}
-
-namespace {
-// the plain rANS decoders of host_rans.cpp on one host core, ns per symbol:
-// measured on the MI355X box's cores with 16 chains at once, the -3 bench's
-// 44.5 M-symbol sequence chains and 22 M-symbol packed qualities
-// (profiles/hostrans_step_trace.txt: 0.92-0.98 and 1.36-1.39)
-constexpr double HOST_RANS_O0_NS = 1.0, HOST_RANS_O1_NS = 1.4;
-// the encoder's bare chains (host_rans.cpp rans_enc_chain_o0 / _o1) on one core
-// of the same box, ns per symbol: tools/host_rans_enc_check --time over 44.5 M
-// symbols of the -3 bench's alphabets, alone and with 16 at once 0.64 and
-// 0.83-0.84 ("Encode long rANS chains on host cores")
-constexpr double HOST_RANS_ENC_O0_NS = 0.65, HOST_RANS_ENC_O1_NS = 0.85;
-// ns per symbol [kind][gpu]: priors from r04 on MI355X boxes (host: this
-// file's decoders on one core of the box, the -5 Illumina hybrid step; GPU:
-// k_fqz_dec_small 170-190, the general decoder with sequence contexts
-// 350-470, k_seq_dec 290-380).  The plain rANS 4x16 chains: GPU 54.4 ns a
-// step of 4 symbols for order-0 and 73.4 for order-1;
-// host: HOST_RANS_O0_NS / _O1_NS above.  The encoder's bare chains: GPU 18.3 ns
-// a step of 4 symbols for both orders (k_enc_chain2w);
-// host: HOST_RANS_ENC_O0_NS / _O1_NS above
-std::atomic<double> g_ns[CK_N][2] = {{{30.0}, {330.0}}, {{16.0}, {180.0}}, {{24.0}, {400.0}},
-                                     {{HOST_RANS_O0_NS}, {13.6}}, {{HOST_RANS_O1_NS}, {18.4}},
-                                     {{HOST_RANS_ENC_O0_NS}, {4.6}}, {{HOST_RANS_ENC_O1_NS}, {4.6}}};
-}  // namespace
-
-double chain_ns(int kind, bool gpu) { return g_ns[kind][gpu ? 1 : 0].load(std::memory_order_relaxed); }
-
-void chain_measured(int kind, bool gpu, double ns) {
-    if (!(ns > 0.0) || kind < 0 || kind >= CK_N) return;
-    std::atomic<double> &a = g_ns[kind][gpu ? 1 : 0];
-    double cur = a.load(std::memory_order_relaxed);
-    // an exponential average: a chain's cost moves with its data
-    while (!a.compare_exchange_weak(cur, 0.5 * cur + 0.5 * ns, std::memory_order_relaxed)) {}
-}
-
-std::vector<char> plan(const std::vector<uint64_t> &n, const std::vector<int> &kind, int threads,
-                       const std::vector<double> *core_ns, std::vector<double> *committed) {
-    std::vector<char> host(n.size(), 0);
-    std::vector<size_t> ord(n.size());
-    for (size_t i = 0; i < ord.size(); i++) ord[i] = i;
-    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) {
-        return double(n[a]) * chain_ns(kind[a], false) > double(n[b]) * chain_ns(kind[b], false);
-    });
-    std::vector<double> core(size_t(std::max(threads, 1)), 0.0);   // each core's finish time
-    if (core_ns) core = *core_ns;
-    if (core.empty()) {                      // no core to give: every chain on the GPU
-        if (committed) committed->clear();
-        return host;
-    }
-    double gpu_t = 0.0;
-    for (size_t i : ord) {
-        auto lo = std::min_element(core.begin(), core.end());
-        const double th = *lo + double(n[i]) * chain_ns(kind[i], false);
-        const double tg = double(n[i]) * chain_ns(kind[i], true);
-        double cmax = 0.0;
-        for (double c : core) cmax = std::max(cmax, c);
-        const double on_host = std::max({cmax, th, gpu_t});
-        const double on_gpu = std::max({cmax, gpu_t, tg});
-        if (on_host <= on_gpu) {
-            *lo = th;
-            host[i] = 1;
-        } else {
-            gpu_t = std::max(gpu_t, tg);
-        }
-    }
-    if (committed) *committed = core;
-    return host;
-}
-
-int cores_of_rank() {
-    // the cores this process may run on (its affinity mask, which
-    // hardware_concurrency() ignores: a cgroup or taskset share), split
-    // evenly among the ranks of this node that share it
-    // ($LOCAL_WORLD_SIZE, set by torch.distributed.run), and no more than
-    // the per-GPU CPU share the box states ($OMP_NUM_THREADS)
-    int n = 0;
-    cpu_set_t set;
-    CPU_ZERO(&set);
-    if (sched_getaffinity(0, sizeof set, &set) == 0) n = CPU_COUNT(&set);
-    if (n <= 0) n = int(std::max(1u, std::thread::hardware_concurrency()));
-    if (const char *e = std::getenv("LOCAL_WORLD_SIZE")) {
-        const int w = std::atoi(e);
-        if (w > 1) n /= w;
-    }
-    if (const char *e = std::getenv("OMP_NUM_THREADS")) {
-        const int o = std::atoi(e);
-        if (o > 0) n = std::min(n, o);
-    }
-    return std::max(1, n);
-}
-
-int threads() {
-    static const int n = [] {
-        if (const char *e = std::getenv("FQZ5_HOST_THREADS")) return std::max(1, std::atoi(e));
-        return std::min(16, cores_of_rank());
-    }();
-    return n;
 }
 
 }  // namespace host

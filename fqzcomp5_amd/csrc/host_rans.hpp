@@ -5,7 +5,7 @@
 // interleaved states over 16-bit words.  One chain is serial whoever runs it;
 // a host core steps it several times faster than a GPU wave, and
 // Decompressor::run_djs (rans_decompress.cpp) places the long ones here by
-// the cost model of host_dec.hpp.  The encoder's bare chains (the states at
+// the cost model of host_sched.hpp.  The encoder's bare chains (the states at
 // every chunk, no output words) follow below: Compressor::stage_encode
 // (rans_compress.cpp) places those the same way.  No HIP in this file or its
 // .cpp.

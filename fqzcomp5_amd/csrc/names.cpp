@@ -5,8 +5,6 @@
 // decoder's unlzp of a name section runs on a host core (host_lzp.cpp) unless
 // host decoding is off.
 #include <algorithm>
-#include <atomic>
-#include <chrono>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -15,7 +13,6 @@
 #include <mutex>
 #include <thread>
 
-#include "host_dec.hpp"
 #include "host_lzp.hpp"
 #include "names.hpp"
 #include "rans_format.hpp"
@@ -26,38 +23,10 @@ namespace {
 void put32(uint8_t *p, uint32_t v) { std::memcpy(p, &v, 4); }
 uint32_t get32(const uint8_t *p) { uint32_t v; std::memcpy(&v, p, 4); return v; }
 
-// fn(i) for i < n on up to 16 host threads
-template <class F> void on_threads(size_t n, F fn) {
-    const size_t hw = size_t(host::threads());
-    if (n <= 1 || hw == 1) {
-        for (size_t i = 0; i < n; i++) fn(i);
-        return;
-    }
-    std::atomic<size_t> next{0};
-    std::exception_ptr err;
-    std::mutex mu;
-    auto work = [&] {
-        try {
-            for (size_t i; (i = next.fetch_add(1)) < n;) fn(i);
-        } catch (...) {
-            std::lock_guard<std::mutex> lk(mu);
-            if (!err) err = std::current_exception();
-        }
-    };
-    std::vector<std::thread> th;
-    for (size_t t = 1; t < std::min(hw, n); t++) th.emplace_back(work);
-    work();
-    for (auto &t : th) t.join();
-    if (err) std::rethrow_exception(err);
-}
-bool trace() {
-    static const bool on = std::getenv("FQZ5_STEP_TRACE") != nullptr;
-    return on;
-}
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(
-               std::chrono::steady_clock::now().time_since_epoch()).count();
-}
+// fn(i) for i < n on the host threads
+void on_threads(size_t n, const std::function<void(size_t)> &fn) { host::parallel_for(n, fn, 1, 2); }
+using host::now_ms;
+using host::step_trace;
 }  // namespace
 
 void name_prepare(const uint8_t *h, uint32_t name_len, int strat, int level, NameEnc &E,
@@ -225,7 +194,7 @@ void names_encode_batch(GpuCtx &g, std::vector<NameEnc> &jobs,
                         const std::vector<const uint8_t *> &d_names,
                         const std::vector<uint32_t> &lens, const std::vector<int> &methods,
                         const std::vector<hipEvent_t> *ready) {
-    const double t0 = trace() ? now_ms() : 0;
+    const double t0 = step_trace() ? now_ms() : 0;
     // TLZP3 candidates (strat 0) need no tokenising: their lzp pass and
     // rANS stream run on the GPU (one helper thread) while the host threads
     // tokenise the others; the comment lzp passes of strat 2 follow.
@@ -273,14 +242,14 @@ void names_encode_batch(GpuCtx &g, std::vector<NameEnc> &jobs,
         if (ready) FQZ5_HIP(hipEventSynchronize((*ready)[k]));
         name_split(h_names[k], lens[k], name_strat(methods[k]), name_level(methods[k]), jobs[k]);
     });
-    const double ts = trace() ? now_ms() : 0;
+    const double ts = step_trace() ? now_ms() : 0;
     if (gpu_search && !groups.empty()) {
         std::vector<Tok3SearchJob *> sp;
         for (size_t i = 0; i < groups.size(); i++)
             if (lens[groups[i][0]]) sp.push_back(&sj[i]);
         if (!sp.empty()) tok3_search_batch(g, sp);
     }
-    const double tsd = trace() ? now_ms() : 0;
+    const double tsd = step_trace() ? now_ms() : 0;
     size_t on_host = 0;
     for (size_t i = 0; i < groups.size(); i++) on_host += !sj[i].ok;
     // the comments' lzp passes (strat 2) need the split only: their inputs go
@@ -317,7 +286,7 @@ void names_encode_batch(GpuCtx &g, std::vector<NameEnc> &jobs,
             if (!lz1.empty()) lzp_encode_batch(g, lz1);
             for (size_t k : early) name_add_requests(g, jobs[k], lz0, rq0);
             if (!rq0.empty()) compress_batch(g, rq0);
-            if (trace()) t_early = now_ms();
+            if (step_trace()) t_early = now_ms();
         } catch (...) {
             err0 = std::current_exception();
         }
@@ -341,19 +310,19 @@ void names_encode_batch(GpuCtx &g, std::vector<NameEnc> &jobs,
         gpu_early.join();
         throw;
     }
-    const double t1 = trace() ? now_ms() : 0;
+    const double t1 = step_trace() ? now_ms() : 0;
     gpu_early.join();
     if (err0) std::rethrow_exception(err0);
-    const double t1b = trace() ? now_ms() : 0;
+    const double t1b = step_trace() ? now_ms() : 0;
     const double t2 = t1b;
     for (const auto &gr : groups)
         for (size_t x = 0; x < gr.size(); x++)
             name_add_requests(g, jobs[gr[x]], lz1, rq1, x ? &jobs[gr[0]] : nullptr);
     if (!rq1.empty()) compress_batch(g, rq1);
-    const double t3 = trace() ? now_ms() : 0;
+    const double t3 = step_trace() ? now_ms() : 0;
     for (size_t k : early) name_assemble(g, jobs[k], rq0);
     for (size_t k : late) name_assemble(g, jobs[k], rq1);
-    if (trace())
+    if (step_trace())
         std::fprintf(stderr, "names encode: %zu candidates, split %.1f ms, GPU trie searches "
                      "%.1f ms (%zu of %zu sections on the host), tokenise %.1f ms (TLZP3 and the "
                      "comment lzp passes on the GPU beside it: done at %.1f ms), waited %.1f ms, "
@@ -583,7 +552,7 @@ namespace {
 // then rebuilt on the host threads
 void names_decode_batch_gpu(GpuCtx &g, std::vector<NameDec> &jobs,
                             const std::function<void(size_t)> &block_done) {
-    const double t0 = trace() ? now_ms() : 0;
+    const double t0 = step_trace() ? now_ms() : 0;
     std::vector<DecompressReq> reqs;
     std::vector<char> good(jobs.size());
     for (size_t k = 0; k < jobs.size(); k++) {
@@ -595,13 +564,13 @@ void names_decode_batch_gpu(GpuCtx &g, std::vector<NameDec> &jobs,
     for (size_t k = 0; k < jobs.size(); k++)
         if (good[k]) name_dec_add_lzp(g, jobs[k], reqs, lz);
     if (!lz.empty()) lzp_decode_batch(g, lz);
-    const double t1 = trace() ? now_ms() : 0;
+    const double t1 = step_trace() ? now_ms() : 0;
     for (size_t k = 0; k < jobs.size(); k++)
         if (good[k]) name_dec_fetch(g, jobs[k], reqs, lz);
         else jobs[k].fetched = false;
-    const double t2 = trace() ? now_ms() : 0;
+    const double t2 = step_trace() ? now_ms() : 0;
     on_threads(jobs.size(), [&](size_t k) { name_dec_rebuild(jobs[k]); });
-    if (trace())
+    if (step_trace())
         std::fprintf(stderr, "names decode: %zu sections, %zu rANS streams + lzp %.1f ms, "
                      "fetch %.1f ms, rebuild %.1f ms\n", jobs.size(), reqs.size(), t1 - t0,
                      t2 - t1, now_ms() - t2);
@@ -682,7 +651,7 @@ void names_decode_batch(GpuCtx &g, std::vector<NameDec> &jobs,
     }
     tasks.join();
     if (err) std::rethrow_exception(err);
-    if (trace()) {
+    if (step_trace()) {
         double f0 = 0, f1 = 0, d0 = 0, d1 = 0, ul = 0, rb = 0;
         uint64_t lz_c = 0, lz_i = 0, lz_o = 0;           // the lzp streams: coded, as lzp, expanded
         for (size_t k = 0; k < jobs.size(); k++) {

@@ -17,11 +17,9 @@
 // capacity failures (NULL returns) are decided in stage 6 from sizes: they
 // never change the bytes of a successful call.
 #include <sys/syscall.h>
-#include <time.h>
 #include <unistd.h>
 #include <algorithm>
 #include <map>
-#include <chrono>
 #include <climits>
 #include <condition_variable>
 #include <deque>
@@ -30,7 +28,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
-#include <exception>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -42,6 +39,11 @@
 #include "rans_format.hpp"
 
 namespace fqz5 {
+
+using host::now_ms;
+using host::now_ns;
+using host::step_trace;
+using host::thread_cpu_ns;
 
 namespace {
 
@@ -119,19 +121,9 @@ struct StripeReq {
 // input is copied to pinned memory, a pool thread runs its chain into pinned
 // checkpoints, and those are uploaded to the job's EncJob::ck, where the
 // replay passes find them as if k_enc_chain2w had left them.
-constexpr uint32_t HOST_CHAIN_MIN = 1u << 20;    // shorter chains are not worth a core (mode 2)
 std::atomic<uint64_t> g_enc_host{0}, g_enc_gpu{0};   // fqz5_rans_enc_chain_counts
 
 inline int enc_chain_kind(const EJ &j) { return j.o1 ? host::CK_RANS_ENC_O1 : host::CK_RANS_ENC_O0; }
-inline double thread_cpu_ns() {
-    timespec t;
-    if (clock_gettime(CLOCK_THREAD_CPUTIME_ID, &t)) return 0;
-    return double(t.tv_sec) * 1e9 + double(t.tv_nsec);
-}
-inline double now_ns() {
-    return std::chrono::duration<double, std::nano>(
-               std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 // What every batch of the process shares (several compress_batch calls plan
 // and run at the same moment from the main, plain, stripe and names threads):
@@ -170,15 +162,15 @@ class EncHost {
         std::unique_lock<std::mutex> lk(g.m);
         g.cv.wait(lk, [&] { return g.left == 0; });
     }
-    // host::plan against the cores' committed finish times, which then
-    // include these chains
-    std::vector<char> plan(const std::vector<uint64_t> &n, const std::vector<int> &kind) {
+    // host::place against the cores' committed finish times, which then
+    // include the chains a plan (mode 2) placed
+    std::vector<char> plan(int mode, const std::vector<uint64_t> &n, const std::vector<int> &kind) {
         std::lock_guard<std::mutex> lk(m_);
         const double now = now_ns();
         acct_.resize(size_t(host::threads()), 0.0);
         std::vector<double> cores(acct_.size()), committed;
         for (size_t i = 0; i < cores.size(); i++) cores[i] = std::max(0.0, acct_[i] - now);
-        std::vector<char> on = host::plan(n, kind, int(cores.size()), &cores, &committed);
+        std::vector<char> on = host::place(mode, n, kind, host::CHAIN_MIN, &cores, &committed);
         for (size_t i = 0; i < committed.size() && i < acct_.size(); i++) acct_[i] = now + committed[i];
         return on;
     }
@@ -636,12 +628,8 @@ void Compressor::build_o1(EJ &j, const uint32_t *cnt) {
 }
 
 void Compressor::stage_tables() {
-    static const bool trace = std::getenv("FQZ5_STEP_TRACE") != nullptr;
-    auto now = [] {
-        return std::chrono::duration<double, std::milli>(
-                   std::chrono::steady_clock::now().time_since_epoch()).count();
-    };
-    const double ta = trace ? now() : 0;
+    const bool trace = step_trace();
+    const double ta = trace ? now_ms() : 0;
     // byte histograms of job inputs made in stage 4 (RLE literals, meta)
     std::vector<std::pair<const uint8_t *, uint32_t>> segs;
     std::vector<int> who;
@@ -696,26 +684,21 @@ void Compressor::stage_tables() {
         for (int z = 1; z < j.nx; z++) j.seg_first[z] = pb[q++];
         j.last_byte = pb[q++];
     }
-    const double tb = trace ? now() : 0;
+    const double tb = trace ? now_ms() : 0;
     host_parallel(o1jobs.size(), [&](size_t k) { build_o1(jobs_[o1jobs[k]], &h[jobs_[o1jobs[k]].f1_off]); });
     if (trace)
         std::fprintf(stderr, "[tid %ld] tables: o1 hist %.1f ms, build_o1 %.1f ms (%zu jobs, %u pairs)\n", long(syscall(SYS_gettid)),
-                     tb - ta, now() - tb, o1jobs.size(), total);
+                     tb - ta, now_ms() - tb, o1jobs.size(), total);
 }
 
 // Stage 5: all rANS chains.  O1 tables above 1000 bytes get their own
 // O0-4x16 job (rANS_static16_int.h:397-412) in the same launch.
 void Compressor::stage_encode() {
-    static const bool trace = std::getenv("FQZ5_STEP_TRACE") != nullptr;
-    auto now = [] {
-        return std::chrono::duration<double, std::milli>(
-                   std::chrono::steady_clock::now().time_since_epoch()).count();
-    };
-    const double ta = trace ? now() : 0;
+    const bool trace = step_trace();
+    const double ta = trace ? now_ms() : 0;
     const size_t nmain = jobs_.size();
-    // the chains on host cores (host_encode_mode(): 0 none, 1 every NX = 4
-    // chain, 2 by host::plan among those of 2^20 symbols and more, 3 every
-    // other one).  Their inputs exist once what the stream holds now has run.
+    // the chains on host cores (host::place by host_encode_mode() among the
+    // NX = 4 chains).  Their inputs exist once what the stream holds now has run.
     const int hmode = host_encode_mode();
     HostChains hc(g_);
     hipEvent_t in_ready = nullptr;
@@ -755,16 +738,12 @@ void Compressor::stage_encode() {
     if (hmode) {
         std::vector<int> el;                     // eligible chains, longest first
         for (int i : order)
-            if (jobs_[i].nx == 4 && (hmode != 2 || jobs_[i].n >= HOST_CHAIN_MIN)) el.push_back(i);
-        if (hmode == 2 && !el.empty()) {
-            std::vector<uint64_t> n;
-            std::vector<int> kind;
-            for (int i : el) { n.push_back(jobs_[i].n); kind.push_back(enc_chain_kind(jobs_[i])); }
-            const std::vector<char> on = EncHost::get().plan(n, kind);
-            for (size_t k = 0; k < el.size(); k++) on_host[el[k]] = on[k];
-        } else {
-            for (size_t k = 0; k < el.size(); k++) on_host[el[k]] = hmode == 1 || k % 2 == 0;
-        }
+            if (jobs_[i].nx == 4) el.push_back(i);
+        std::vector<uint64_t> n;
+        std::vector<int> kind;
+        for (int i : el) { n.push_back(jobs_[i].n); kind.push_back(enc_chain_kind(jobs_[i])); }
+        const std::vector<char> on = EncHost::get().plan(hmode, n, kind);
+        for (size_t k = 0; k < el.size(); k++) on_host[el[k]] = on[k];
         // pinned input (one per (d_in, n): RANS0 and RANS1 of a section share
         // it) and checkpoints; a chain whose buffers the budget refuses stays
         // on the GPU
@@ -796,11 +775,11 @@ void Compressor::stage_encode() {
             hipStream_t cs = EncHost::get().copy_stream();
             std::map<const uint8_t *, hipEvent_t> ev_of;
             hipEvent_t shared = nullptr;
-            t_copy0 = now();
+            t_copy0 = now_ms();
             for (const auto &key : copy_order) {
                 uint8_t *dst = copies[key];
                 FQZ5_HIP(hipMemcpyAsync(dst, key.first, key.second, hipMemcpyDeviceToHost, cs));
-                if (key.second >= HOST_CHAIN_MIN) {
+                if (key.second >= host::CHAIN_MIN) {
                     ev_of[dst] = hc.event(hipEventDisableTiming);
                     FQZ5_HIP(hipEventRecord(ev_of[dst], cs));
                 } else {
@@ -819,7 +798,7 @@ void Compressor::stage_encode() {
             std::vector<std::function<void()>> tasks;
             const int dev = g_.device;
             for (size_t k = 0; k < hc.chains.size(); k++)
-                tasks.push_back([this, &hc, k, dev, &now] {
+                tasks.push_back([this, &hc, k, dev] {
                     HostChains::Chain &c = hc.chains[k];
                     const EJ &j = jobs_[c.job];
                     if (c.landed) {
@@ -829,7 +808,7 @@ void Compressor::stage_encode() {
                         if (hipEventQuery(c.landed) != hipSuccess) {
                             (void)hipGetLastError();
                             FQZ5_HIP(hipEventSynchronize(c.landed));
-                            c.landed_ms = now();
+                            c.landed_ms = now_ms();
                         }
                     }
                     const double a = now_ns(), ca = thread_cpu_ns();
@@ -874,7 +853,7 @@ void Compressor::stage_encode() {
         tab_off[i] = nsyms + all_syms.size();
         all_syms.insert(all_syms.end(), j.syms.begin(), j.syms.end());
     }
-    const double tb = trace ? now() : 0;
+    const double tb = trace ? now_ms() : 0;
     EncSym *d_syms = g_.arena.alloc_n<EncSym>(std::max<size_t>(nsyms + all_syms.size(), 1));
     if (!all_syms.empty()) {
         uint8_t *st = g_.staging.alloc(all_syms.size() * sizeof(EncSym));
@@ -937,14 +916,14 @@ void Compressor::stage_encode() {
     // output lengths are known, below
     long tk_2w = -1, tk_1w = -1, tk_r0 = -1, tk_r1 = -1;
     // a chain launch's time over its longest chain is the GPU's cost of that
-    // chain's kind (host::chain_measured, as the decoder's launches give it)
+    // chain's kind (host::measured, as the decoder's launches give it)
     auto timed = [&](int longest) {
-        return hmode && longest >= 0 && jobs_[longest].nx == 4 && jobs_[longest].n >= HOST_CHAIN_MIN;
+        return hmode && longest >= 0 && jobs_[longest].nx == 4 && jobs_[longest].n >= host::CHAIN_MIN;
     };
     hipEvent_t ts[2] = {nullptr, nullptr}, tl[2] = {nullptr, nullptr};
     if (timed(long_s)) { ts[0] = hc.event(hipEventDefault); ts[1] = hc.event(hipEventDefault); }
     if (timed(long_b)) { tl[0] = hc.event(hipEventDefault); tl[1] = hc.event(hipEventDefault); }
-    const double t_launch = now();
+    const double t_launch = now_ms();
     if (!ejs.empty()) {
         const EncJob *d = g_.upload(ejs);
         const EncJob *db = ejb.empty() ? nullptr : g_.upload(ejb);
@@ -979,7 +958,7 @@ void Compressor::stage_encode() {
     double host_joined = 0, host_longest = 0, first_landed = 0, last_landed = 0;
     if (!hc.chains.empty()) {
         hc.join();
-        host_joined = now() - t_launch;
+        host_joined = now_ms() - t_launch;
         if (hc.group.failed) throw GpuError("rANS encode: a host chain failed");
         for (const HostChains::Chain &c : hc.chains) {
             const EJ &j = jobs_[c.job];
@@ -993,8 +972,7 @@ void Compressor::stage_encode() {
             // that shared its core with the name tokenisers or a waiting
             // helper thread (2-4x, from step to step) made the next plan leave
             // long chains on the GPU, 205 ms each.
-            if (j.n >= HOST_CHAIN_MIN)
-                host::chain_measured(enc_chain_kind(j), false, (c.cpu_ns > 0 ? c.cpu_ns : c.ns) / double(j.n));
+            host::measured(enc_chain_kind(j), false, j.n, c.cpu_ns > 0 ? c.cpu_ns : c.ns);
             FQZ5_HIP(hipMemcpyAsync(ck_of[c.job], c.ck, c.words * 4, hipMemcpyHostToDevice, g_.stream));
         }
     }
@@ -1013,11 +991,11 @@ void Compressor::stage_encode() {
         tk_r1 = sp.end(0);
     }
     ev.stop(g_.stream);
-    const double tc = trace ? now() : 0;
+    const double tc = trace ? now_ms() : 0;
     std::vector<uint32_t> lens(jobs_.size(), 0);
     g_.download(lens.data(), d_lens, jobs_.size());
     g_.sync();
-    const double td = trace ? now() : 0;
+    const double td = trace ? now_ms() : 0;
     if (ev.on || tk_r1 >= 0) {
         double bytes = 0, b2w = 0, b1w = 0;
         for (int i : order) {
@@ -1039,7 +1017,7 @@ void Compressor::stage_encode() {
     auto gpu_measured = [&](hipEvent_t *e, int longest) {
         float ms = 0;
         if (e[0] && hipEventElapsedTime(&ms, e[0], e[1]) == hipSuccess)
-            host::chain_measured(enc_chain_kind(jobs_[longest]), true, double(ms) * 1e6 / double(jobs_[longest].n));
+            host::measured(enc_chain_kind(jobs_[longest]), true, jobs_[longest].n, double(ms) * 1e6);
     };
     gpu_measured(ts, long_s);
     gpu_measured(tl, long_b);
@@ -1049,7 +1027,7 @@ void Compressor::stage_encode() {
     if (trace) {
         std::fprintf(stderr, "[tid %ld] encode: tables %.1f ms (%zu syms), uploads+launch %.1f ms, "
                      "wait %.1f ms, finish %.1f ms", long(syscall(SYS_gettid)), tb - ta, nsyms + all_syms.size(), tc - tb,
-                     td - tc, now() - td);
+                     td - tc, now_ms() - td);
         if (hmode)
             std::fprintf(stderr, "; host chains %zu of %zu (longest %.1f ms, joined %.1f ms after the launch, "
                          "chains waited for input copies that landed %.1f .. %.1f ms after the first was issued), ns per symbol "
@@ -1214,8 +1192,7 @@ bool Compressor::stripe_layout(const StripeReq &S, const CompressReq &r, Layout 
 
 // ---------------------------------------------------------------------------
 void Compressor::run(std::vector<CompressReq> &reqs) {
-    const double t_enter = std::chrono::duration<double, std::milli>(
-                               std::chrono::steady_clock::now().time_since_epoch()).count();
+    const double t_enter = now_ms();
     std::vector<int> req_leaf(reqs.size(), -1), req_stripe(reqs.size(), -1);
     std::vector<StripeItem> sitems;
     uint32_t max_n = 0;
@@ -1256,17 +1233,13 @@ void Compressor::run(std::vector<CompressReq> &reqs) {
     }
     if (!sitems.empty())
         FQZ5_HIP(launch_stripe(g_.upload(sitems), int(sitems.size()), max_n, g_.stream));
-    static const bool trace = std::getenv("FQZ5_STEP_TRACE") != nullptr;
-    auto now = [] {
-        return std::chrono::duration<double, std::milli>(
-                   std::chrono::steady_clock::now().time_since_epoch()).count();
-    };
-    const double t0 = trace ? now() : 0;
+    const bool trace = step_trace();
+    const double t0 = trace ? now_ms() : 0;
     if (trace) std::fprintf(stderr, "[tid %ld] compress: leaves %.1f ms\n", long(syscall(SYS_gettid)), t0 - t_enter);
     stage_pack();
-    const double t1 = trace ? now() : 0;
+    const double t1 = trace ? now_ms() : 0;
     stage_rle();
-    const double t2 = trace ? now() : 0;
+    const double t2 = trace ? now_ms() : 0;
     for (auto &L : leaves_) {
         uint32_t n = L.n_cur;
         if (L.rle) {
@@ -1285,11 +1258,11 @@ void Compressor::run(std::vector<CompressReq> &reqs) {
             std::memcpy(jobs_[L.ej_main].F0, L.pack ? L.phist : L.hist, 1024);
         }
     }
-    const double t3 = trace ? now() : 0;
+    const double t3 = trace ? now_ms() : 0;
     stage_tables();
-    const double t4 = trace ? now() : 0;
+    const double t4 = trace ? now_ms() : 0;
     stage_encode();
-    const double t5 = trace ? now() : 0;
+    const double t5 = trace ? now_ms() : 0;
     if (trace)
         std::fprintf(stderr, "[tid %ld] compress: pack %.1f ms, rle %.1f ms, jobs %.1f ms, tables %.1f ms, "
                      "encode %.1f ms (%zu requests, %zu jobs)\n", long(syscall(SYS_gettid)), t1 - t0, t2 - t1, t3 - t2,
@@ -1300,8 +1273,7 @@ void Compressor::run(std::vector<CompressReq> &reqs) {
         ~Done() {
             if (on)
                 std::fprintf(stderr, "[tid %ld] compress: layouts %.1f ms\n", long(syscall(SYS_gettid)),
-                             std::chrono::duration<double, std::milli>(
-                                 std::chrono::steady_clock::now().time_since_epoch()).count() - t);
+                             now_ms() - t);
         }
     } done_{trace, t5};
     for (size_t i = 0; i < reqs.size(); i++) {
@@ -1336,20 +1308,16 @@ void rans_enc_chain_counts(uint64_t *out2) {
 }
 
 void compress_batch(GpuCtx &g, std::vector<CompressReq> &reqs) {
-    static const bool trace = std::getenv("FQZ5_STEP_TRACE") != nullptr;
-    auto now = [] {
-        return std::chrono::duration<double, std::milli>(
-                   std::chrono::steady_clock::now().time_since_epoch()).count();
-    };
+    const bool trace = step_trace();
     std::unique_ptr<Compressor> c(new Compressor(g));
     c->run(reqs);
-    const double t0 = trace ? now() : 0;
+    const double t0 = trace ? now_ms() : 0;
     // A batch of thousands of jobs frees ~100 MB of host tables and
     // layouts (130 ms at -5, mostly munmap); the results no longer refer to
     // them, so a detached thread frees them off the caller's critical path.
     if (c->njobs() > 1000) std::thread([p = c.release()] { delete p; }).detach();
     else c.reset();
-    if (trace) std::fprintf(stderr, "[tid %ld] compress: teardown %.1f ms\n", long(syscall(SYS_gettid)), now() - t0);
+    if (trace) std::fprintf(stderr, "[tid %ld] compress: teardown %.1f ms\n", long(syscall(SYS_gettid)), now_ms() - t0);
 }
 
 // ---------------------------------------------------------------------------

@@ -7,18 +7,16 @@
 //   B  all O0 / O1 chains (main data and RLE meta-data)
 //   C  RLE expansion, D  un-packing, E  stripe interleave.
 // A chain of stage B with 4 states may instead decode on a host core
-// (host_rans.cpp) beside the launch, where the cost model of host_dec.hpp
+// (host_rans.cpp) beside the launch, where the cost model of host_sched.hpp
 // finishes the batch sooner (run_djs); its bytes are uploaded in stream order
 // before stages C-E.
 #include <atomic>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
 #include <climits>
 #include <cstring>
 
-#include "host_dec.hpp"
 #include "host_rans.hpp"
 #include "kernels.h"
 #include "rans_codec.hpp"
@@ -319,29 +317,19 @@ static bool o1_keys(const DJ &j, DecJob &d) {
     return true;
 }
 
-// $FQZ5_STEP_TRACE: host wall time of the decode phases on stderr
-static bool step_trace() {
-    static const bool on = std::getenv("FQZ5_STEP_TRACE") != nullptr;
-    return on;
-}
-static double now_ms() {
-    return std::chrono::duration<double, std::milli>(
-               std::chrono::steady_clock::now().time_since_epoch()).count();
-}
+using host::now_ms;
+using host::now_ns;
+using host::step_trace;
 
 std::atomic<uint64_t> g_rans_host{0}, g_rans_gpu{0};   // fqz5_rans_chain_counts
 
-// a chain's kind for the cost model, and the chains too short to be worth a
-// core: under 2^20 symbols a chain costs the launch under ~20 ms beside the
-// others
-constexpr uint32_t HOST_CHAIN_MIN = 1u << 20;
+// a chain's kind for the cost model
 inline int chain_kind(const DJ &j) { return j.o1 ? host::CK_RANS_O1 : host::CK_RANS_O0; }
 
 void Decompressor::run_djs(const std::vector<int> &ids, bool may_host) {
-    // ---- the chains that decode on host cores (host_decode_mode(): 0 none,
-    // 1 every 4-state chain, 2 by host::plan among those of 2^20 symbols and
-    // more, 3 every other one).  They start now, into pinned staging, and
-    // are joined after the launch below.
+    // ---- the chains that decode on host cores (host::place by
+    // host_decode_mode() among the 4-state chains).  They start now, into
+    // pinned staging, and are joined after the launch below.
     struct HostChain { int id; uint8_t *buf; bool ok; double ns; };
     std::vector<HostChain> hc;
     std::vector<char> on_host(djs_.size(), 0);
@@ -352,21 +340,15 @@ void Decompressor::run_djs(const std::vector<int> &ids, bool may_host) {
         for (int id : ids) {
             const DJ &j = djs_[id];
             if (!j.ok || !j.n || j.nx != 4 || j.len < j.tab_len + 16u) continue;
-            if (hmode == 2 && j.n < HOST_CHAIN_MIN) continue;
             el.push_back(id);
         }
-        std::vector<double> idle(size_t(host::threads()), 0.0);
-        const std::vector<double> &cores = cores_ ? cores_->core_ns : idle;
-        host_threads = cores.size();
-        if (hmode == 2 && !el.empty()) {
-            std::vector<uint64_t> n;
-            std::vector<int> kind;
-            for (int id : el) { n.push_back(djs_[id].n); kind.push_back(chain_kind(djs_[id])); }
-            const std::vector<char> on = host::plan(n, kind, int(cores.size()), &cores);
-            for (size_t k = 0; k < el.size(); k++) on_host[el[k]] = on[k];
-        } else if (host_threads) {
-            for (size_t k = 0; k < el.size(); k++) on_host[el[k]] = hmode == 1 || k % 2 == 0;
-        }
+        host_threads = cores_ ? cores_->core_ns.size() : size_t(host::threads());
+        std::vector<uint64_t> n;
+        std::vector<int> kind;
+        for (int id : el) { n.push_back(djs_[id].n); kind.push_back(chain_kind(djs_[id])); }
+        const std::vector<char> on = host::place(hmode, n, kind, host::CHAIN_MIN,
+                                                 cores_ ? &cores_->core_ns : nullptr);
+        for (size_t k = 0; k < el.size(); k++) on_host[el[k]] = on[k];
         for (int id : el)
             if (on_host[id]) hc.push_back({id, g_.staging.alloc(size_t(djs_[id].n) + 1), false, 0.0});
         // the threads take them longest first, as the plan placed them
@@ -380,7 +362,7 @@ void Decompressor::run_djs(const std::vector<int> &ids, bool may_host) {
     hjobs.start(hc.size(), [&](size_t k) {
         HostChain &c = hc[k];
         const DJ &j = djs_[c.id];
-        const auto a = std::chrono::steady_clock::now();
+        const double a = now_ns();
         const uint8_t *in = j.h + j.tab_len;
         const size_t in_len = j.len - j.tab_len;
         if (j.o1) {
@@ -391,7 +373,7 @@ void Decompressor::run_djs(const std::vector<int> &ids, bool may_host) {
         } else {
             c.ok = host::rans_dec_o0(j.F.data(), j.bits, in, in_len, c.buf, j.n);
         }
-        c.ns = std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - a).count();
+        c.ns = now_ns() - a;
     }, host_threads);
     // joined, judged and uploaded behind the launch in stream order
     auto finish_host = [&] {
@@ -404,7 +386,7 @@ void Decompressor::run_djs(const std::vector<int> &ids, bool may_host) {
             DJ &j = djs_[c.id];
             host_longest_ms_ = std::max(host_longest_ms_, c.ns * 1e-6);
             if (!c.ok) { j.ok = false; continue; }
-            if (j.n >= HOST_CHAIN_MIN) host::chain_measured(chain_kind(j), false, c.ns / double(j.n));
+            host::measured(chain_kind(j), false, j.n, c.ns);
             FQZ5_HIP(hipMemcpyAsync(j.d_out, c.buf, j.n, hipMemcpyHostToDevice, g_.stream));
         }
     };
@@ -543,7 +525,7 @@ void Decompressor::run_djs(const std::vector<int> &ids, bool may_host) {
     }
     lds = g_.chain_lds(lds, djs.size());
     g_rans_gpu += ord.size();
-    const auto launch_t0 = std::chrono::steady_clock::now();
+    const double launch_t0 = now_ns();
     if (!djs.empty()) FQZ5_HIP(launch_dec(g_.upload(djs), int(djs.size()), lds, g_.stream));
     ev.stop(g_.stream);
     std::vector<int32_t> st(used.size());
@@ -552,10 +534,7 @@ void Decompressor::run_djs(const std::vector<int> &ids, bool may_host) {
     // the launch's time over its longest chain: the GPU cost of that chain's kind
     if (!ord.empty()) {
         const DJ &lj = djs_[used[ord[0]]];
-        if (lj.nx == 4 && lj.n >= HOST_CHAIN_MIN)
-            host::chain_measured(chain_kind(lj), true,
-                                 std::chrono::duration<double, std::nano>(
-                                     std::chrono::steady_clock::now() - launch_t0).count() / double(lj.n));
+        if (lj.nx == 4) host::measured(chain_kind(lj), true, lj.n, now_ns() - launch_t0);
     }
     finish_host();
     if (ev.on) {

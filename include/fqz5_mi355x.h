@@ -217,7 +217,7 @@ void fqz5_rans_enc_chain_counts(uint64_t *out2);
  * (bad arguments, or a byte or pair of the input without a frequency). */
 uint32_t *fqz5_rans_enc_chain_host(const unsigned char *in, size_t n, int order, int bits,
                                    const uint32_t *freq, size_t *ck_words);
-/* The chain placement of the cost model (host_dec.hpp plan) for `count`
+/* The chain placement of the cost model (host_sched.hpp plan) for `count`
  * chains of n[i] symbols and kind[i] (0 sequence model, 1 fqz, 2 fqz with a
  * sequence context, 3 rANS order-0, 4 rANS order-1, 5 / 6 the encoder's bare
  * rANS order-0 / order-1 chain) on `threads` host cores

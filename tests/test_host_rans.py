@@ -118,7 +118,7 @@ def test_sanitized_program(tmp_path, golden_rans):
     assert " 0 bad" in r.stdout
 
 
-# ---- the placement plan (host_dec.cpp plan) ---------------------------------
+# ---- the placement plan (host_sched.cpp plan) -------------------------------
 
 CK_RANS_O0, CK_RANS_O1 = 3, 4
 

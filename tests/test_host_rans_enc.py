@@ -110,7 +110,7 @@ def test_sanitized_program(tmp_path):
     assert "ns per symbol" in r.stdout
 
 
-# ---- the placement plan with the encoder's kinds (host_dec.cpp plan) ---------
+# ---- the placement plan with the encoder's kinds (host_sched.cpp plan) -------
 
 CK_RANS_ENC_O0, CK_RANS_ENC_O1 = 5, 6
 

@@ -76,6 +76,8 @@ def test_one_long_chain(mode, long_chain):
         assert g1 == g0 and h1 == h0 + 1
     if mode == 2:
         assert (h1 - h0) + (g1 - g0) == 1
+    if mode == 3:                                      # the one eligible chain is position 0
+        assert h1 == h0 + 1 and g1 == g0
 
 
 @pytest.fixture(scope="module")
