@@ -18,11 +18,14 @@
 // records (record ranges read through the file's block index): the records'
 // sizes, their output offsets and the sequence offsets are computed and
 // scanned on the device, and the host sees the totals only.
+// fqz5_fastq_format_list does the same for an ascending list of records (the
+// hits of a lookup by read name, name_match.hip).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "../../include/fqz5_fastq.h"
@@ -467,15 +470,16 @@ __global__ void k_fq_flags(const fqz5_fastq_rec *recs, uint64_t a, uint64_t n, c
 // output_fastq (fqzcomp5.c:3441-3480): '@' name '\n' seq '\n' '+' [name] '\n'
 // qual+33 '\n'; without qualities output_fasta (:3503-3517): '>' name '\n'
 // seq '\n'.  One wave per record: wave j writes record base + j of the block
-// (zpos, soff and lens are the block's) at ooff[j].
+// (sel: record sel[j], a list checked by k_fq_sizes; zpos, soff and lens are
+// the block's) at ooff[j].
 __global__ void k_fq_format(const uint8_t *names, const uint64_t *zpos, const uint8_t *seq,
                             const uint8_t *qual, const uint64_t *soff, const uint32_t *lens,
-                            const uint64_t *ooff, uint64_t base, uint64_t n, int plus_name,
-                            uint8_t *out) {
+                            const uint64_t *ooff, uint64_t base, const uint32_t *sel, uint64_t n,
+                            int plus_name, uint8_t *out) {
     const uint64_t j = (uint64_t(blockIdx.x) * blockDim.x + threadIdx.x) / 64;
     const uint32_t lane = threadIdx.x & 63;
     if (j >= n) return;
-    const uint64_t k = base + j;
+    const uint64_t k = sel ? sel[j] : base + j;
     const uint64_t ns = k ? zpos[k - 1] + 1 : 0;
     const uint32_t nl = uint32_t(zpos[k] - ns), L = lens[k];
     uint8_t *o = out + ooff[j];
@@ -511,13 +515,25 @@ __global__ void k_fq_format(const uint8_t *names, const uint64_t *zpos, const ui
 // record) from the name terminators and the lengths; entry n is 0, so an
 // exclusive scan over n + 1 entries ends with the total.  odd (pairs): the
 // even records' sizes into size (0 for an odd record), the odd ones' into odd.
-__global__ void k_fq_sizes(const uint64_t *zpos, const uint32_t *lens, uint64_t base, uint64_t n,
-                           int fastq, int plus_name, uint64_t *size, uint64_t *odd) {
+// sel: records sel[0..n) instead (fqz5_fastq_format_list), which must
+// ascend strictly and stay below nrec; an entry that does not sets *bad and
+// counts nothing, so no later kernel is launched on the list.
+__global__ void k_fq_sizes(const uint64_t *zpos, const uint32_t *lens, uint64_t base,
+                           const uint32_t *sel, uint64_t nrec, uint64_t n, int fastq, int plus_name,
+                           uint64_t *size, uint64_t *odd, uint32_t *bad) {
     const uint64_t j = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (j > n) return;
     uint64_t sz = 0;
-    const uint64_t k = base + j;
-    if (j < n) {
+    uint64_t k = base + j;
+    bool ok = j < n;
+    if (sel && ok) {
+        k = sel[j];
+        if (k >= nrec || (j && sel[j - 1] >= k)) {
+            atomicOr(bad, 1u);
+            ok = false;
+        }
+    }
+    if (ok) {
         const uint64_t nl = zpos[k] - (k ? zpos[k - 1] + 1 : 0), L = lens[k];
         sz = fastq ? 1 + nl + 1 + L + 2 + (plus_name ? nl : 0) + 1 + L + 1 : 1 + nl + 1 + L + 1;
     }
@@ -531,11 +547,11 @@ __global__ void k_fq_sizes(const uint64_t *zpos, const uint32_t *lens, uint64_t 
 
 // pairs: the scanned even offsets (oe) and odd offsets (oo) into one offset
 // per record, the odd records' text after all the even ones' (oe[n])
-__global__ void k_fq_pair_offsets(const uint64_t *oe, const uint64_t *oo, uint64_t base, uint64_t n,
-                                  uint64_t *ooff) {
+__global__ void k_fq_pair_offsets(const uint64_t *oe, const uint64_t *oo, uint64_t base,
+                                  const uint32_t *sel, uint64_t n, uint64_t *ooff) {
     const uint64_t j = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (j >= n) return;
-    ooff[j] = ((base + j) & 1) ? oe[n] + oo[j] : oe[j];
+    ooff[j] = ((sel ? sel[j] : base + j) & 1) ? oe[n] + oo[j] : oe[j];
 }
 
 dim3 grid_for(uint64_t n, uint32_t per) { return dim3(uint32_t((n + per - 1) / per ? (n + per - 1) / per : 1)); }
@@ -738,6 +754,12 @@ bool four_line(GpuCtx &g, const uint8_t *d_text, const uint64_t *lines, uint64_t
 }
 
 }  // namespace
+
+// find_delims for name_match.hip (the name terminators of a section)
+uint64_t *fastq_find_delims(GpuCtx &g, const uint8_t *d_text, uint64_t len, uint8_t ch,
+                            uint64_t *count) {
+    return find_delims(g, d_text, len, ch, count);
+}
 }  // namespace fqz5
 
 using namespace fqz5;
@@ -1022,7 +1044,8 @@ static int format_impl(const uint8_t *d_names, uint64_t name_len, const uint8_t 
         const uint32_t *d_l = g.upload(h_len, nrec);
         if (nrec)
             hipLaunchKernelGGL(k_fq_format, grid_for(nrec * 64, 256), dim3(256), 0, g.stream, d_names, z,
-                               d_seq, d_qual, d_so, d_l, d_oo, uint64_t(0), nrec, plus_name, d_out);
+                               d_seq, d_qual, d_so, d_l, d_oo, uint64_t(0),
+                               static_cast<const uint32_t *>(nullptr), nrec, plus_name, d_out);
         FQZ5_HIP(hipGetLastError());
         g.reset();
         return 0;
@@ -1049,52 +1072,55 @@ int fqz5_fastq_format_pairs(const uint8_t *d_names, uint64_t name_len, const uin
                        out_len, r1_len ? r1_len : &dummy);
 }
 
-// Records [rec_first, rec_first + rec_count) of a block, laid out on the
-// device: the sizes of the slice's records (k_fq_sizes), their exclusive
-// scans for the output offsets (pairs: the even records', then the odd ones'
-// placed after the even total) and the scan of the lengths before the slice
-// end for the sequence offsets.  The host sees the totals only.
-int fqz5_fastq_format_range(const uint8_t *d_names, uint64_t name_len, const uint8_t *d_seq,
-                            const uint8_t *d_qual, const uint32_t *h_len, uint64_t nrec,
-                            uint64_t rec_first, uint64_t rec_count, int plus_name, int pairs,
-                            uint8_t *d_out, uint64_t out_cap, uint64_t *out_len,
-                            uint64_t *r1_len) {
+// Records of a block, laid out on the device: a range [rec_first, rec_first +
+// n) (d_sel NULL) or the list d_sel[0..n).  The sizes of those records
+// (k_fq_sizes), their exclusive scans for the output offsets (pairs: the even
+// records', then the odd ones' placed after the even total) and the scan of
+// the lengths of records [0, end) for the sequence offsets (a range: end its
+// own end; a list: every record).  The host sees the totals only.
+static int format_part(const char *what, const uint8_t *d_names, uint64_t name_len,
+                       const uint8_t *d_seq, const uint8_t *d_qual, const uint32_t *h_len,
+                       uint64_t nrec, uint64_t rec_first, const uint32_t *d_sel, uint64_t n,
+                       uint64_t end, int plus_name, int pairs, uint8_t *d_out, uint64_t out_cap,
+                       uint64_t *out_len, uint64_t *r1_len) {
     GpuCtx *gp = nullptr;
+    const std::string pre = std::string(what) + ": ";
     try {
-        if (rec_first > nrec || rec_count > nrec - rec_first)
-            throw GpuError("fastq_format_range: the slice runs past the block's records");
-        *out_len = 0;
-        if (r1_len) *r1_len = 0;
-        if (!rec_count) return 0;
-        const uint64_t end = rec_first + rec_count, n = rec_count;
-        if (end >= (1ull << 31)) throw GpuError("fastq_format_range: block too large");
+        if (end >= (1ull << 31)) throw GpuError(pre + "block too large");
         GpuCtx &g = gpu();
         gp = &g;
         uint64_t nz = 0;
         uint64_t *z = find_delims(g, d_names, name_len, 0, &nz);
-        if (nz < end) throw GpuError("fastq_format_range: fewer names than records");
+        if (nz < end) throw GpuError(pre + "fewer names than records");
         const uint32_t *d_l = g.upload(h_len, end);
-        // soff: bases before each record, over every record before the slice end
+        // soff: bases before each record, over every record before `end`
         uint64_t *l64 = g.arena.alloc_n<uint64_t>(size_t(end));
         uint64_t *soff = g.arena.alloc_n<uint64_t>(size_t(end));
         hipLaunchKernelGGL(k_widen, grid_for(end, 256), dim3(256), 0, g.stream, d_l, l64, end);
         FQZ5_HIP(hipGetLastError());
         excl_sum(g, l64, soff, end);
-        // ooff: text bytes before each record of the slice; entry n the total
+        // ooff: text bytes before each of the n records; entry n the total
         uint64_t *sz = g.arena.alloc_n<uint64_t>(size_t(n) + 1);
         uint64_t *ooff = g.arena.alloc_n<uint64_t>(size_t(n) + 1);
         uint64_t *szo = pairs ? g.arena.alloc_n<uint64_t>(size_t(n) + 1) : nullptr;
-        hipLaunchKernelGGL(k_fq_sizes, grid_for(n + 1, 256), dim3(256), 0, g.stream, z, d_l, rec_first, n,
-                           d_qual ? 1 : 0, plus_name, sz, szo);
+        uint32_t *bad = nullptr;
+        if (d_sel) {
+            bad = g.arena.alloc_n<uint32_t>(1);
+            g.memset0(bad, 4);
+        }
+        hipLaunchKernelGGL(k_fq_sizes, grid_for(n + 1, 256), dim3(256), 0, g.stream, z, d_l, rec_first,
+                           d_sel, nrec, n, d_qual ? 1 : 0, plus_name, sz, szo, bad);
         FQZ5_HIP(hipGetLastError());
         uint64_t tot[2] = {0, 0};
+        uint32_t h_bad = 0;
+        if (bad) g.download(&h_bad, bad, 1);
         if (pairs) {
             uint64_t *oe = g.arena.alloc_n<uint64_t>(size_t(n) + 1);
             uint64_t *oo = g.arena.alloc_n<uint64_t>(size_t(n) + 1);
             excl_sum(g, sz, oe, n + 1);
             excl_sum(g, szo, oo, n + 1);
             hipLaunchKernelGGL(k_fq_pair_offsets, grid_for(n, 256), dim3(256), 0, g.stream, oe, oo, rec_first,
-                               n, ooff);
+                               d_sel, n, ooff);
             FQZ5_HIP(hipGetLastError());
             g.download(&tot[0], oe + n, 1);
             g.download(&tot[1], oo + n, 1);
@@ -1103,12 +1129,13 @@ int fqz5_fastq_format_range(const uint8_t *d_names, uint64_t name_len, const uin
             g.download(&tot[0], ooff + n, 1);
         }
         g.sync();
+        if (h_bad) throw GpuError(pre + "the record list does not ascend or reaches past the block's records");
         *out_len = tot[0] + tot[1];
         if (r1_len) *r1_len = pairs ? tot[0] : *out_len;
         if (!d_out) { g.reset(); return 0; }
-        if (*out_len > out_cap) throw GpuError("fastq_format_range: output larger than out_cap");
+        if (*out_len > out_cap) throw GpuError(pre + "output larger than out_cap");
         hipLaunchKernelGGL(k_fq_format, grid_for(n * 64, 256), dim3(256), 0, g.stream, d_names, z, d_seq,
-                           d_qual, soff, d_l, ooff, rec_first, n, plus_name, d_out);
+                           d_qual, soff, d_l, ooff, rec_first, d_sel, n, plus_name, d_out);
         FQZ5_HIP(hipGetLastError());
         g.reset();
         return 0;
@@ -1117,6 +1144,38 @@ int fqz5_fastq_format_range(const uint8_t *d_names, uint64_t name_len, const uin
         try { if (gp) gp->reset(); } catch (...) {}
         return -1;
     }
+}
+
+int fqz5_fastq_format_range(const uint8_t *d_names, uint64_t name_len, const uint8_t *d_seq,
+                            const uint8_t *d_qual, const uint32_t *h_len, uint64_t nrec,
+                            uint64_t rec_first, uint64_t rec_count, int plus_name, int pairs,
+                            uint8_t *d_out, uint64_t out_cap, uint64_t *out_len,
+                            uint64_t *r1_len) {
+    if (rec_first > nrec || rec_count > nrec - rec_first) {
+        fqz5_set_error("fastq_format_range: the slice runs past the block's records");
+        return -1;
+    }
+    *out_len = 0;
+    if (r1_len) *r1_len = 0;
+    if (!rec_count) return 0;
+    return format_part("fastq_format_range", d_names, name_len, d_seq, d_qual, h_len, nrec, rec_first,
+                       nullptr, rec_count, rec_first + rec_count, plus_name, pairs, d_out, out_cap,
+                       out_len, r1_len);
+}
+
+int fqz5_fastq_format_list(const uint8_t *d_names, uint64_t name_len, const uint8_t *d_seq,
+                           const uint8_t *d_qual, const uint32_t *h_len, uint64_t nrec,
+                           const uint32_t *d_sel, uint64_t n_sel, int plus_name, int pairs,
+                           uint8_t *d_out, uint64_t out_cap, uint64_t *out_len, uint64_t *r1_len) {
+    *out_len = 0;
+    if (r1_len) *r1_len = 0;
+    if (!n_sel) return 0;
+    if (n_sel > nrec) {                  // (no strictly ascending list below nrec is that long)
+        fqz5_set_error("fastq_format_list: more records listed than the block holds");
+        return -1;
+    }
+    return format_part("fastq_format_list", d_names, name_len, d_seq, d_qual, h_len, nrec, 0, d_sel,
+                       n_sel, nrec, plus_name, pairs, d_out, out_cap, out_len, r1_len);
 }
 
 }  // extern "C"

@@ -1,0 +1,41 @@
+// name_match.hpp — the query table of lookup by read name (name_match.hip):
+// the hash the host builder and the device kernel share, and the table's
+// slot rule.
+//
+// A key is hashed byte by byte (FNV-1a's step, so a lane of k_name_match
+// carries the state across its staging windows) and mixed once at the key's
+// end.  The mixed value's low bits give the first slot of the open-addressing
+// probe, its top tag_bits the slot's tag.  A tag only spares byte
+// comparisons: a match is decided by the bytes alone.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace fqz5 {
+
+constexpr uint32_t NM_NONE = 0xFFFFFFFFu;       // no query / an empty slot
+constexpr uint32_t NM_HASH0 = 2166136261u;      // the state before a key's first byte
+
+// the state after byte c; with last: the key has ended, c is ignored and the
+// state is mixed (murmur3's finaliser) into the value slots and tags come from
+__host__ __device__ inline uint32_t nm_hash(uint32_t h, uint8_t c, bool last = false) {
+    if (!last) return (h ^ c) * 16777619u;
+    h ^= h >> 16;
+    h *= 0x85ebca6bu;
+    h ^= h >> 13;
+    h *= 0xc2b2ae35u;
+    h ^= h >> 16;
+    return h;
+}
+
+__host__ __device__ inline uint32_t nm_tag(uint32_t mixed, int tag_bits) {
+    return tag_bits >= 32 ? mixed : mixed >> (32 - tag_bits);
+}
+
+// one slot: the tag in the low word, the query index (NM_NONE: empty) above
+__host__ __device__ inline uint64_t nm_slot(uint32_t tag, uint32_t query) {
+    return uint64_t(query) << 32 | tag;
+}
+
+}  // namespace fqz5

@@ -21,6 +21,15 @@ fqzcomp5 writes, produced and read by this library alone.
                                      the wanted records, laid out on the
                                      device); with_qual=False: no quality
                                      section decoded, FASTA text
+    find_names(src, names) / extract_names_file(src, dst, names[, dst2=]) /
+    extract_names_bytes: records by read name, in one pass over the file:
+                                     every block read and checked, only its
+                                     name section decoded, the names matched
+                                     against the query table on the device
+                                     (fqz5_names_match) -> sequence and
+                                     quality decoded for the blocks with hits
+                                     only -> fqz5_fastq_format_list (the hit
+                                     records' text, in file order)
 
 File layout (fqzcomp5.c:2563-2630, :2959-2969): "FQZ5\\1\\1\\0\\0", u64 index
 offset, the blocks, then "FQZ5IDX\\0", u32 nblocks and per block {u64 file
@@ -96,6 +105,22 @@ def _load():
                                                C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
                                                C.c_int, C.c_int, C.c_void_p, C.c_uint64,
                                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        so.fqz5_fastq_format_list.restype = C.c_int
+        so.fqz5_fastq_format_list.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                              C.c_int, C.c_int, C.c_void_p, C.c_uint64,
+                                              C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        so.fqz5_names_table_build.restype = C.c_void_p
+        so.fqz5_names_table_build.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_int]
+        so.fqz5_names_table_free.restype = None
+        so.fqz5_names_table_free.argtypes = [C.c_void_p]
+        so.fqz5_names_table_find.restype = C.c_int64
+        so.fqz5_names_table_find.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64]
+        so.fqz5_names_match_window.restype = C.c_uint32
+        so.fqz5_names_match_window.argtypes = []
+        so.fqz5_names_match.restype = C.c_int
+        so.fqz5_names_match.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int,
+                                        C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
         _bound = True
     return so
 
@@ -103,7 +128,10 @@ def _load():
 # $FQZ5_FILE_TRACE: host wall time per stage of compress_file /
 # decompress_file on stderr (read, upload, parse, gather, codec, assemble,
 # download, write; extract_file: index, read, upload, decode, format,
-# download, write); the stages end with what the library synchronises
+# download, write; find_names / extract_names_file: index, read, upload,
+# names (the blocks parsed and CRC-checked, their name sections decoded),
+# match, decode, format, download, write); the stages end with what the
+# library synchronises
 _TRACE = {}
 
 
@@ -1331,31 +1359,13 @@ def check_blocks(data, ranges=None) -> list[dict]:
     return [block_fields(data, s, e, v) for s, e in ranges]
 
 
-def _decode(data, buf, plus_name: bool, device: str, pairs: bool = False, ranges=None,
-            slices=None, with_qual: bool = True):
-    """Blocks of a .fqz5 (host view `data`, device copy `buf`; `ranges` the
-    block byte ranges within them, all blocks of the file by default) ->
-    the FASTQ text of every block in one device buffer; pairs: (the R1
-    text, the R2 text) of output_fastq_deinterleaved (fqzcomp5.c:3612-3676),
-    even records of every block to R1 and odd ones to R2.
-
-    slices: per block (rec_first, rec_count), the records whose text is
-    wanted (extract_file): every block is still decoded whole, and its text
-    is laid out by fqz5_fastq_format_range for those records only.
-    with_qual False: the quality sections are not decoded and the text is
-    output_fasta's ('>' name, sequence)."""
-    import contextlib
-    import torch
-    so = _load()
-    # (the range path's $FQZ5_FILE_TRACE stages; whole-file callers time the call)
-    st_dec = _stage("decode") if slices is not None else contextlib.nullcontext()
-    st_fmt = _stage("format") if slices is not None else contextlib.nullcontext()
-    st_dec.__enter__()
-    if ranges is None:
-        ranges = _blocks_of(data)
+def _parse_checked(data, buf, ranges):
+    """The blocks `ranges` of a container (host view `data`, device copy
+    `buf`) checked and parsed: their header fields on the host
+    (check_blocks), then fqz5_blocks_parse_v on the device with the CRC of
+    every block.  Returns the BlockViews, the record lengths and whether each
+    block is FASTA."""
     version = getattr(ranges, "version", V11)
-    if not ranges:
-        return torch.empty(0, dtype=torch.uint8, device=device)
     try:
         check_blocks(data, ranges)
     except ValueError as err:
@@ -1379,6 +1389,34 @@ def _decode(data, buf, plus_name: bool, device: str, pairs: bool = False, ranges
     # FASTA: a quality section of u_len 0 and c_len 0 (decode_block,
     # fqzcomp5.c:2477-2483); the text is then output_fasta's (:3503-3517)
     fasta = [v.qual_ulen == 0 and v.qual_size == 9 for v in views]
+    return views, lens, fasta
+
+
+def _decode(data, buf, plus_name: bool, device: str, pairs: bool = False, ranges=None,
+            slices=None, with_qual: bool = True):
+    """Blocks of a .fqz5 (host view `data`, device copy `buf`; `ranges` the
+    block byte ranges within them, all blocks of the file by default) ->
+    the FASTQ text of every block in one device buffer; pairs: (the R1
+    text, the R2 text) of output_fastq_deinterleaved (fqzcomp5.c:3612-3676),
+    even records of every block to R1 and odd ones to R2.
+
+    slices: per block (rec_first, rec_count), the records whose text is
+    wanted (extract_file): every block is still decoded whole, and its text
+    is laid out by fqz5_fastq_format_range for those records only.
+    with_qual False: the quality sections are not decoded and the text is
+    output_fasta's ('>' name, sequence)."""
+    import contextlib
+    import torch
+    so = _load()
+    # (the range path's $FQZ5_FILE_TRACE stages; whole-file callers time the call)
+    st_dec = _stage("decode") if slices is not None else contextlib.nullcontext()
+    st_fmt = _stage("format") if slices is not None else contextlib.nullcontext()
+    st_dec.__enter__()
+    if ranges is None:
+        ranges = _blocks_of(data)
+    if not ranges:
+        return torch.empty(0, dtype=torch.uint8, device=device)
+    views, lens, fasta = _parse_checked(data, buf, ranges)
     nsz = [v.name_ulen for v in views]
     ssz = [v.seq_ulen for v in views]
     out_d = torch.empty(sum(nsz) + 2 * sum(ssz) + 1, dtype=torch.uint8, device=device)
@@ -1805,6 +1843,17 @@ def cover(index, first: int, count: int) -> list[tuple[int, int, int]]:
     return out
 
 
+def _check_entry(index, b: int, hv, a: int) -> None:
+    """Block b as read (hv holds the file from offset a on) against its index
+    entry: the size and record count in its header are the index's."""
+    s, t, n = index[b]
+    bsz, nrec = struct.unpack_from("<II", hv, s - a) if t - s >= 8 else (None, None)
+    if bsz != t - s - 4 or nrec != n:
+        raise _lib.NativeError(
+            f"index disagrees with block {b}: size {bsz} records {nrec} in its header, "
+            f"size {t - s - 4} records {n} in the index")
+
+
 def _extract_windows(rd, first: int, count: int, plus_name: bool, device: str, pairs: bool,
                      with_qual: bool, window_bytes: int | None):
     """The text of records [first, first + count) (pairs: of pairs) of the
@@ -1833,12 +1882,7 @@ def _extract_windows(rd, first: int, count: int, plus_name: bool, device: str, p
             if len(hv) != e - a:
                 raise _lib.NativeError("index disagrees with the file: a block past its end")
         for b, _, _ in grp:
-            s, t, n = index[b]
-            bsz, nrec = struct.unpack_from("<II", hv, s - a) if t - s >= 8 else (None, None)
-            if bsz != t - s - 4 or nrec != n:
-                raise _lib.NativeError(
-                    f"index disagrees with block {b}: size {bsz} records {nrec} in its header, "
-                    f"size {t - s - 4} records {n} in the index")
+            _check_entry(index, b, hv, a)
         with _stage("upload"):
             buf = torch.from_numpy(np.ascontiguousarray(hv)).to(device)   # blocking
         texts = _decode(hv, buf, plus_name, device, pairs=pairs,
@@ -1863,6 +1907,37 @@ def extract_bytes(data, first: int, count: int, plus_name: bool = False, device:
     return b"".join(out)
 
 
+def _write_texts(outs, windows) -> list[int]:
+    """The windows' texts (per window one device tensor per output) to the
+    files `outs`: plain outputs by positioned writes as the windows come,
+    gzip ones held and written whole.  Returns the bytes written per output."""
+    sinks = [None if d.endswith(".gz") else _Sink(d, True) for d in outs]
+    held = [[] for _ in outs]
+    written = [0 for _ in outs]
+    try:
+        for texts in windows:
+            for j, t in enumerate(texts):
+                with _stage("download"):
+                    out = _pinned(int(t.numel()))
+                    out.copy_(t)
+                with _stage("write"):
+                    if sinks[j] is not None:
+                        sinks[j].write_at(written[j], out.numpy())
+                    else:
+                        held[j].append(out.numpy().tobytes())
+                    written[j] += int(t.numel())
+                del out
+    finally:
+        for sk in sinks:
+            if sk is not None:
+                sk.close()
+    with _stage("write"):
+        for d, sk, h in zip(outs, sinks, held):
+            if sk is None:
+                _write_out(d, b"".join(h))
+    return written
+
+
 def extract_file(src: str, dst: str, first: int, count: int, plus_name: bool = False,
                  device: str = "cuda", dst2: str | None = None, with_qual: bool = True,
                  window_bytes: int | None = None) -> int:
@@ -1877,34 +1952,306 @@ def extract_file(src: str, dst: str, first: int, count: int, plus_name: bool = F
     quality section is decoded and the text is FASTA.  A ".gz" destination is
     gzip-compressed.  One process; returns the text bytes written."""
     pairs = dst2 is not None
-    outs = [dst] + ([dst2] if pairs else [])
-    # plain outputs by positioned writes as the windows come, gzip ones whole
-    sinks = [None if d.endswith(".gz") else _Sink(d, True) for d in outs]
-    held = [[] for _ in outs]
-    written = [0 for _ in outs]
     rd = _PosFile(src)
     try:
-        for texts in _extract_windows(rd, first, count, plus_name, device, pairs, with_qual,
-                                      window_bytes):
-            for j, t in enumerate(texts):
-                with _stage("download"):
-                    out = _pinned(int(t.numel()))
-                    out.copy_(t)
-                with _stage("write"):
-                    if sinks[j] is not None:
-                        sinks[j].write_at(written[j], out.numpy())
-                    else:
-                        held[j].append(out.numpy().tobytes())
-                    written[j] += int(t.numel())
-                del out
+        written = _write_texts([dst] + ([dst2] if pairs else []),
+                               _extract_windows(rd, first, count, plus_name, device, pairs, with_qual,
+                                                window_bytes))
     finally:
         rd.close()
-        for sk in sinks:
-            if sk is not None:
-                sk.close()
-    with _stage("write"):
-        for d, sk, h in zip(outs, sinks, held):
-            if sk is None:
-                _write_out(d, b"".join(h))
     _trace_dump("extract")
     return sum(written)
+
+
+# ---------------------------------------------------------------------------
+# Lookup by read name
+#
+# A caller holds read names, not record numbers.  Names are in no order the
+# index knows, so every block's name section is decoded, in one pass over the
+# file: each window of blocks is read once, checked against the index,
+# uploaded, parsed and CRC-checked whole (the CRC covers the block, and a
+# skipped check could turn damage into a silent miss); then only its SEC_NAME
+# sections go to the section decoder, and fqz5_names_match (name_match.hip)
+# finds each block's records whose key is in the query table, on the device.
+# Only the compacted hits come back to the host.  The extractors then decode
+# the sequence (and quality) sections of the blocks with hits alone and lay
+# out the text of the hit records with fqz5_fastq_format_list.  Output is in
+# file order; a name several records carry yields all of them.  One process;
+# no name index is kept between calls; "/1" and "/2" are part of a name.
+# ---------------------------------------------------------------------------
+class NameHits:
+    """The result of a lookup by name: `records` (np.uint64) the file record
+    numbers that matched, ascending (pairs: with their mates); `query`
+    (np.int64) per record the index into the caller's names of the name it
+    carries (the first occurrence of a name given twice), -1 for a mate taken
+    only as partner; `missing` the names no record matched, in the caller's
+    order; `written` the text bytes written (extract_names_file)."""
+
+    def __init__(self, records, query, missing, written: int = 0):
+        self.records, self.query, self.missing, self.written = records, query, missing, written
+
+
+def read_name_list(path) -> list[bytes]:
+    """A list of read names, one per line: the line end ('\\n', "\\r\\n") is
+    dropped and empty lines are skipped; nothing else is stripped (a leading
+    '@' stays part of the name)."""
+    with open(path, "rb") as f:
+        return [x for x in (ln.rstrip(b"\r\n") for ln in f) if x]
+
+
+def _queries(names):
+    """The caller's names as (the names as given, the distinct names as
+    bytes in order of first occurrence, for each of those the index of that
+    first occurrence).  str names are UTF-8; an empty name is a ValueError."""
+    given = list(names)
+    qs, first, seen = [], [], set()
+    for i, x in enumerate(given):
+        b = x.encode() if isinstance(x, str) else bytes(x)
+        if not b:
+            raise ValueError(f"read name {i} is empty")
+        if b"\0" in b:
+            raise ValueError(f"read name {i} holds a NUL byte")
+        if b not in seen:
+            seen.add(b)
+            qs.append(b)
+            first.append(i)
+    return given, qs, first
+
+
+def _name_hits(given, first, records, qidx, written: int = 0) -> NameHits:
+    """NameHits from the matcher's output: qidx per record the index of the
+    distinct query it carries (0xFFFFFFFF: none, a mate)."""
+    records = np.asarray(records, np.uint64)
+    qidx = np.asarray(qidx, np.uint32)
+    none = qidx == 0xFFFFFFFF
+    fa = np.asarray(first, np.int64)
+    query = np.full(len(qidx), -1, np.int64)
+    if len(fa):
+        query[~none] = fa[qidx[~none].astype(np.int64)]
+    found = set(np.unique(qidx[~none]).tolist())
+    missing = [given[i] for q, i in enumerate(first) if q not in found]
+    return NameHits(records, query, missing, written)
+
+
+class _NameTable:
+    """fqz5_name_table of the distinct queries (freed on exit)."""
+
+    def __init__(self, queries: list[bytes], tag_bits: int = 32):
+        self.so = _load()
+        blob = b"".join(q + b"\0" for q in queries)
+        self.p = self.so.fqz5_names_table_build(blob, len(blob), len(queries), tag_bits)
+        if not self.p:
+            raise _lib.NativeError("fqz5_names_table_build: " + _lib.last_error())
+
+    def find(self, key: bytes) -> int:
+        return int(self.so.fqz5_names_table_find(self.p, key, len(key)))
+
+    def close(self) -> None:
+        if self.p:
+            self.so.fqz5_names_table_free(self.p)
+            self.p = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def _names_windows(rd, tab: _NameTable, whole: bool, pairs: bool, extract: bool, plus_name: bool,
+                   with_qual: bool, device: str, window_bytes: int | None):
+    """One pass over the container behind `rd` (see above), window by window:
+    (file record numbers of the window's hits, their query indices, the hits'
+    text as device tensors or None without `extract`; pairs: R1 and R2 text)."""
+    import torch
+    so = _load()
+    with _stage("index"):
+        index = read_index(rd)
+    wb = window_bytes or DEFAULT_WINDOW
+    groups, cur, tot = [], [], 0
+    for b, (s, t, _) in enumerate(index):
+        if cur and tot + t - s > wb:
+            groups.append(cur)
+            cur, tot = [], 0
+        cur.append(b)
+        tot += t - s
+    if cur:
+        groups.append(cur)
+    rec0 = [0]
+    for _, _, n in index:
+        rec0.append(rec0[-1] + int(n))            # (Python ints: more than 2^32 records)
+    for grp in groups:
+        a, e = index[grp[0]][0], index[grp[-1]][1]
+        with _stage("read"):
+            hv = rd.read(a, e)
+            if len(hv) != e - a:
+                raise _lib.NativeError("index disagrees with the file: a block past its end")
+        for b in grp:
+            _check_entry(index, b, hv, a)
+        with _stage("upload"):
+            buf = torch.from_numpy(np.ascontiguousarray(hv)).to(device)   # blocking
+        with _stage("names"):
+            ranges = Blocks([(index[b][0] - a, index[b][1] - a) for b in grp], index.version)
+            views, lens, fasta = _parse_checked(hv, buf, ranges)
+            noff = np.concatenate([[0], np.cumsum([v.name_ulen for v in views])]).astype(np.int64)
+            name_d = torch.empty(int(noff[-1]) + 1, dtype=torch.uint8, device=device)
+            base = buf.data_ptr()
+            rls = [ln.ctypes.data_as(C.POINTER(C.c_uint32)) for ln in lens]
+            secs = [S.Section(base + s + v.name_off, name_d.data_ptr() + int(noff[j]), v.name_size,
+                              v.name_ulen, 0, S.SEC_NAME, rls[j], None, len(lens[j]), None)
+                    for j, ((s, _), v) in enumerate(zip(ranges, views))]
+            if any(r.status != 0 for r in S.decode(secs)):
+                raise _lib.NativeError("section decoding failed: " + _lib.last_error())
+        recs, qidx, sels = [], [], {}
+        with _stage("match"):
+            hits = torch.empty((2, max(max(len(ln) for ln in lens), 1)), dtype=torch.int32,
+                               device=device)
+            for j, (v, ln) in enumerate(zip(views, lens)):
+                n = C.c_uint64(0)
+                _lib.after_torch(device)          # (the last block's hits have been copied)
+                _check(so.fqz5_names_match(tab.p, name_d.data_ptr() + int(noff[j]), v.name_ulen,
+                                           len(ln), int(whole), int(pairs), hits[0].data_ptr(),
+                                           hits[1].data_ptr(), C.byref(n)), "fqz5_names_match")
+                n = int(n.value)
+                if not n:
+                    continue
+                got = hits[:, :n].cpu().numpy().view(np.uint32)      # the compacted hits alone
+                recs.append(got[0].astype(np.uint64) + np.uint64(rec0[grp[j]]))
+                qidx.append(got[1].copy())
+                if extract:
+                    sels[j] = hits[0, :n].clone()
+        recs = np.concatenate(recs) if recs else np.zeros(0, np.uint64)
+        qidx = np.concatenate(qidx) if qidx else np.zeros(0, np.uint32)
+        if not extract:
+            yield recs, qidx, None
+            del buf, hv, name_d
+            continue
+        with _stage("decode"):
+            soff, o = {}, 0
+            for j in sels:
+                soff[j] = o
+                o += 2 * views[j].seq_ulen
+            out_d = torch.empty(o + 1, dtype=torch.uint8, device=device)
+            secs = []
+            for j in sels:
+                (s, _), v = ranges[j], views[j]
+                sp = out_d.data_ptr() + soff[j]
+                secs.append(S.Section(base + s + v.seq_off, sp, v.seq_size, v.seq_ulen, 0,
+                                      S.SEC_SEQ, rls[j], None, len(lens[j]), None))
+                if with_qual and not fasta[j]:
+                    secs.append(S.Section(base + s + v.qual_off, sp + v.seq_ulen, v.qual_size,
+                                          v.qual_ulen, 0, S.SEC_QUAL, rls[j], None, len(lens[j]),
+                                          sp))
+            if secs and any(r.status != 0 for r in S.decode(secs)):
+                raise _lib.NativeError("section decoding failed: " + _lib.last_error())
+        with _stage("format"):
+            def fmt(j, out, cap):
+                v, sp = views[j], out_d.data_ptr() + soff[j]
+                size, s1 = C.c_uint64(0), C.c_uint64(0)
+                _check(so.fqz5_fastq_format_list(
+                    name_d.data_ptr() + int(noff[j]), v.name_ulen, sp,
+                    sp + v.seq_ulen if with_qual and not fasta[j] else None, lens[j].ctypes.data,
+                    len(lens[j]), sels[j].data_ptr(), int(sels[j].numel()), int(plus_name),
+                    int(pairs), out, cap, C.byref(size), C.byref(s1)), "fqz5_fastq_format_list")
+                return int(size.value), int(s1.value)
+            _lib.after_torch(device)
+            sizes = {j: fmt(j, None, 0) for j in sels}
+            text = torch.empty(max(sum(z for z, _ in sizes.values()), 1), dtype=torch.uint8,
+                               device=device)
+            _lib.after_torch(device)
+            at, r1, r2 = 0, [], []
+            for j, (z, k) in sizes.items():
+                fmt(j, text.data_ptr() + at, z)
+                r1.append((at, at + k))
+                r2.append((at + k, at + z))
+                at += z
+        if not pairs:
+            yield recs, qidx, (text[:at],)
+        else:
+            cat = lambda rs: torch.cat([text[x:y] for x, y in rs]) if rs else text[:0]
+            yield recs, qidx, (cat(r1), cat(r2))
+        del buf, hv, name_d, out_d, text
+
+
+def _find(rd, names, whole, pairs, extract, plus_name, with_qual, device, window_bytes, sink):
+    """The lookup over `rd`; sink(windows of texts) consumes the hits' text
+    (extract) and returns the bytes written."""
+    given, qs, first = _queries(names)
+    if not qs:
+        return _name_hits(given, first, [], [], sink(iter(())) if extract else 0)
+    recs, qidx = [], []
+    with _NameTable(qs) as tab:
+        def windows():
+            for r, q, texts in _names_windows(rd, tab, whole, pairs, extract, plus_name, with_qual,
+                                              device, window_bytes):
+                recs.append(r)
+                qidx.append(q)
+                yield texts
+        if extract:
+            written = sink(windows())
+        else:
+            written = 0
+            for _ in windows():
+                pass
+    return _name_hits(given, first, np.concatenate(recs) if recs else [],
+                      np.concatenate(qidx) if qidx else [], written)
+
+
+def find_names(src, names, whole: bool = False, pairs: bool = False, device: str = "cuda",
+               window_bytes: int | None = None) -> NameHits:
+    """The records of a .fqz5 (a path, the file's bytes, or a positioned
+    reader) that carry one of `names` (bytes or str): every block is read,
+    checked and CRC-checked, its name section alone decoded and matched on
+    the GPU (see above); no sequence or quality section is decoded.  A
+    record's key is its name up to the first ' ' or '\\t' (kseq's name), with
+    `whole` the entire header line; keys are compared byte for byte.  pairs:
+    a hit on record 2k or 2k + 1 selects both mates."""
+    rd, close = _reader(src)
+    try:
+        res = _find(rd, names, whole, pairs, False, False, True, device, window_bytes, None)
+    finally:
+        if close:
+            rd.close()
+    _trace_dump("find_names")
+    return res
+
+
+def extract_names_bytes(data, names, whole: bool = False, plus_name: bool = False,
+                        with_qual: bool = True, device: str = "cuda") -> bytes:
+    """The records of a .fqz5 held in memory that carry one of `names`, in
+    file order, as the text decompress_bytes gives for them (with_qual
+    False: FASTA text, no quality section decoded).  See find_names."""
+    out = []
+
+    def sink(windows):
+        for (t,) in windows:
+            out.append(t.cpu().numpy().tobytes())
+        return sum(len(x) for x in out)
+    _find(_PosBytes(data), names, whole, False, True, plus_name, with_qual, device, None, sink)
+    _trace_dump("extract_names")
+    return b"".join(out)
+
+
+def extract_names_file(src: str, dst: str, names, whole: bool = False, plus_name: bool = False,
+                       device: str = "cuda", dst2: str | None = None, with_qual: bool = True,
+                       window_bytes: int | None = None) -> NameHits:
+    """The records of the .fqz5 file src that carry one of `names` to dst, in
+    file order (never query order): one pass over the file in windows of at
+    most `window_bytes` of compressed data; every block is read once, checked
+    against its index entry and CRC-checked, and its name section decoded and
+    matched on the GPU; the sequence and quality sections are decoded for the
+    blocks with hits only, and the hits' text is laid out on the GPU
+    (fqz5_fastq_format_list).  dst2: the records are interleaved pairs, a hit
+    on either mate takes both, R1 records to dst and R2 records to dst2.
+    with_qual False: no quality section is decoded and the text is FASTA.  A
+    ".gz" destination is gzip-compressed.  One process; returns the NameHits
+    (`written`: the text bytes written)."""
+    outs = [dst] + ([dst2] if dst2 is not None else [])
+    rd = _PosFile(src)
+    try:
+        res = _find(rd, names, whole, dst2 is not None, True, plus_name, with_qual, device,
+                    window_bytes, lambda w: sum(_write_texts(outs, w)))
+    finally:
+        rd.close()
+    _trace_dump("extract_names")
+    return res

@@ -26,6 +26,10 @@
  *   fqz5_fastq_format_range  the same text for a range of a block's records
  *                       only (record ranges read through the file's block
  *                       index, fqz5file.extract_file), laid out on the device.
+ *   fqz5_fastq_format_list   the same for an ascending list of its records.
+ *   fqz5_names_*        lookup by read name: a query table built on the host,
+ *                       matched against a decoded name section on the device
+ *                       (fqz5file.find_names / extract_names_file).
  *
  * Offsets are bytes into the text.  Calls return 0 (fqz5_fastq_index: 1 for
  * FASTA text; fqz5_fastq_blocks: the block count) or -1 with
@@ -117,6 +121,57 @@ int fqz5_fastq_format_range(const uint8_t *d_names, uint64_t name_len, const uin
                             uint64_t rec_first, uint64_t rec_count, int plus_name, int pairs,
                             uint8_t *d_out, uint64_t out_cap, uint64_t *out_len,
                             uint64_t *r1_len);
+
+/* fqz5_fastq_format_range for a list of records instead of a range: d_sel
+ * (device, n_sel entries) holds record indices of the block, strictly
+ * ascending and below nrec; the text is exactly the bytes fqz5_fastq_format
+ * (pairs != 0: fqz5_fastq_format_pairs, the listed even records first, the
+ * listed odd ones after them; *r1_len, may be NULL, the first part's size)
+ * writes for those records, in that order.  h_len is read for all nrec
+ * records.  The list is checked on the device: one that does not ascend or
+ * reaches nrec fails the call, as do fewer name terminators than nrec and a
+ * text larger than out_cap.  n_sel 0: *out_len = 0, nothing is launched.
+ * d_out NULL: the sizes only.  The layout is computed on the device as for a
+ * range (the sequence offsets a scan over all lengths, the output offsets a
+ * scan over the listed records' sizes); only the totals come back. */
+int fqz5_fastq_format_list(const uint8_t *d_names, uint64_t name_len, const uint8_t *d_seq,
+                           const uint8_t *d_qual, const uint32_t *h_len, uint64_t nrec,
+                           const uint32_t *d_sel, uint64_t n_sel, int plus_name, int pairs,
+                           uint8_t *d_out, uint64_t out_cap, uint64_t *out_len, uint64_t *r1_len);
+
+/* Lookup by read name (name_match.hip; fqz5file.find_names): a table of
+ * query names built on the host, and the records of a decoded name section
+ * (name [' ' comment] '\0' per record) whose key is one of them.  whole = 0:
+ * a record's key is its name up to the first ' ' or '\t' (kseq's name);
+ * whole != 0: the entire header line up to the '\0'.  Keys are compared byte
+ * for byte; a mate suffix ("/1", "/2") is part of the key. */
+typedef struct fqz5_name_table fqz5_name_table;
+
+/* q: the queries, '\0' after each (the layout of a name section);
+ * tag_bits 1..32: the file path passes 32, fewer only narrows the tag so that
+ * tests reach the byte comparison.  An empty query and a query given twice
+ * are refused (NULL). */
+fqz5_name_table *fqz5_names_table_build(const uint8_t *q, uint64_t q_len, uint64_t nq,
+                                        int tag_bits);
+
+/* the table and its device copy (made by the first fqz5_names_match) */
+void fqz5_names_table_free(fqz5_name_table *);
+
+/* host probe with the kernel's hash and rule: query index or -1 */
+int64_t fqz5_names_table_find(const fqz5_name_table *, const uint8_t *key, uint64_t len);
+
+/* bytes of the kernel's LDS staging window */
+uint32_t fqz5_names_match_window(void);
+
+/* The records of d_names[0..name_len) (device; nrec records) whose key is in
+ * the table: their indices, ascending, into d_rec and each one's query index
+ * into d_query (device, nrec entries each), *n_hit their number.  pairs != 0:
+ * a hit on record 2k or 2k + 1 selects both (a mate past nrec is ignored);
+ * the query index of one that did not match itself is 0xFFFFFFFF.  Fails
+ * when the section has fewer name terminators than nrec. */
+int fqz5_names_match(const fqz5_name_table *, const uint8_t *d_names, uint64_t name_len,
+                     uint64_t nrec, int whole, int pairs,
+                     uint32_t *d_rec, uint32_t *d_query, uint64_t *n_hit);
 
 #ifdef __cplusplus
 }
