@@ -338,6 +338,12 @@ void fqz5_decode_chain_counts(uint64_t *out2) {
 void fqz5_rans_chain_counts(uint64_t *out2) { rans_chain_counts(out2); }
 void fqz5_rans_enc_chain_counts(uint64_t *out2) { rans_enc_chain_counts(out2); }
 
+void fqz5_rans_variant_counts(uint64_t *dec, uint64_t *dec_hedged, uint64_t *enc, int *ndec,
+                              int *nenc) {
+    rans_variant_counts(dec, dec_hedged, enc, ndec, nenc);
+}
+const char *fqz5_rans_variant_name(int dir, int i) { return rans_variant_name(dir, i); }
+
 void fqz5_trial_counts(uint64_t *out2) {
     out2[0] = g_fqz_tried.load();
     out2[1] = g_fqz_pruned.load();

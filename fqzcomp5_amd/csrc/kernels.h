@@ -152,6 +152,47 @@ inline uint32_t dec_table_mode(bool o1, uint32_t rows, int bits) {
     return DEC_TAB_GLOBAL;
 }
 
+// The body of k_rans_dec that decodes a job, from the fields the kernel's
+// dispatch reads (rans_chain.hip k_rans_dec / dec_any), and the encoder chain
+// that codes one (rans_compress.cpp stage_encode): what
+// fqz5_rans_variant_counts counts.  Host side only; the names in this order.
+enum : int {
+    DV_O0_REG1 = 0,                              // .. DV_O0_REG1 + 7: dec4_lean_body<false, K>
+    DV_O0_LEAN = 8,
+    DV_O1_LEAN, DV_O1_LDS, DV_O1_SPLIT, DV_O1_GLOBAL,
+    DV_O1REG1,                                   // .. DV_O1REG1 + 3: dec4_o1reg_body<K>
+    DV_X32_O0 = DV_O1REG1 + 4,
+    DV_X32_O1_LDS, DV_X32_O1_SPLIT, DV_X32_O1_GLOBAL,
+    DV_COUNT
+};
+constexpr const char *DEC_VARIANT_NAMES[DV_COUNT] = {
+    "O0_REG1", "O0_REG2", "O0_REG3", "O0_REG4", "O0_REG5", "O0_REG6", "O0_REG7", "O0_REG8",
+    "O0_LEAN", "O1_LEAN", "O1_LDS", "O1_SPLIT", "O1_GLOBAL",
+    "O1REG1", "O1REG2", "O1REG3", "O1REG4",
+    "X32_O0", "X32_O1_LDS", "X32_O1_SPLIT", "X32_O1_GLOBAL"};
+inline int dec_variant(const DecJob &J) {
+    const int tm = J.mode == DEC_TAB_LDS ? 0 : J.mode == DEC_TAB_SPLIT ? 1 : 2;
+    if (J.alpha != nullptr && J.okeys) {
+        const uint32_t k = J.okeys >> 4;
+        return DV_O1REG1 + (k >= 1 && k <= 3 ? int(k) - 1 : 3);
+    }
+    if (J.alpha != nullptr) {
+        if (J.nx == 32) return DV_X32_O1_LDS + tm;
+        if (J.mode == DEC_TAB_LDS && dec_lean(J.rows, J.bits)) return DV_O1_LEAN;
+        return DV_O1_LDS + tm;
+    }
+    if (J.nx == 32) return DV_X32_O0;
+    return J.nreg >= 1 && J.nreg <= DEC_REG_MAX ? DV_O0_REG1 + int(J.nreg) - 1 : DV_O0_LEAN;
+}
+
+enum : int {
+    EV_E2W_O0 = 0, EV_E2W_O1, EV_E1W_O1_COMPACT, EV_E32_O0, EV_E32_O1, EV_E32_O1_COMPACT,
+    EV_COUNT
+};
+constexpr const char *ENC_VARIANT_NAMES[EV_COUNT] = {
+    "E2W_O0", "E2W_O1", "E1W_O1_COMPACT", "E32_O0", "E32_O1", "E32_O1_COMPACT"};
+// (enc_variant: below, behind enc_chain_2w)
+
 // RLE encode of one leaf input; saved[] marks the RLE symbols.
 struct RleItem {
     const uint8_t *in;
@@ -214,6 +255,12 @@ uint32_t enc_lds_bytes(int o1, uint32_t A);
 uint32_t enc_replay_lds_bytes(int o1, uint32_t A);
 bool enc_chain_2w(int o1, int nx, uint32_t A);       // runs k_enc_chain2w
 uint32_t enc_2w_lds_bytes(int o1, uint32_t A);
+inline int enc_variant(bool o1, int nx, uint32_t A) {
+    if (enc_chain_2w(o1, nx, A)) return o1 ? EV_E2W_O1 : EV_E2W_O0;
+    if (nx == 4) return EV_E1W_O1_COMPACT;       // (NX=4 off k_enc_chain2w: the table is compact)
+    if (!o1) return EV_E32_O0;
+    return enc_tab_compact(true, A) ? EV_E32_O1_COMPACT : EV_E32_O1;
+}
 hipError_t launch_enc_chain2w(const EncJob *d_jobs, int njobs, uint32_t lds, hipStream_t s);
 uint32_t dec_lds_bytes(uint32_t rows, int bits, int mode);
 hipError_t launch_enc_chain(const EncJob *d_jobs, int njobs, uint32_t lds, hipStream_t s);

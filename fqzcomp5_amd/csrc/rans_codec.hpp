@@ -74,5 +74,11 @@ void decompress_batch(GpuCtx &g, std::vector<DecompressReq> &reqs,
 void rans_chain_counts(uint64_t *out2);
 // the encoder's chains placed so far: out2[0] on host cores, out2[1] on the GPU
 void rans_enc_chain_counts(uint64_t *out2);
+// GPU-launched jobs by kernel body (kernels.h dec_variant / enc_variant):
+// dec[*ndec], those of them launched in several hedged copies, enc[*nenc];
+// null arrays are skipped.  rans_variant_name: dir 0 dec[i], 1 enc[i].
+void rans_variant_counts(uint64_t *dec, uint64_t *dec_hedged, uint64_t *enc, int *ndec, int *nenc);
+const char *rans_variant_name(int dir, int i);
+void rans_enc_variant_counts(uint64_t *enc);    // (the encoder's part, rans_compress.cpp)
 
 }  // namespace fqz5

@@ -122,6 +122,7 @@ struct StripeReq {
 // checkpoints, and those are uploaded to the job's EncJob::ck, where the
 // replay passes find them as if k_enc_chain2w had left them.
 std::atomic<uint64_t> g_enc_host{0}, g_enc_gpu{0};   // fqz5_rans_enc_chain_counts
+std::atomic<uint64_t> g_enc_variant[EV_COUNT];       // fqz5_rans_variant_counts: GPU-launched chains
 
 inline int enc_chain_kind(const EJ &j) { return j.o1 ? host::CK_RANS_ENC_O1 : host::CK_RANS_ENC_O0; }
 
@@ -901,6 +902,8 @@ void Compressor::stage_encode() {
             ejb.push_back(e);
             lds_b = std::max(lds_b, enc_lds_bytes(j.o1, uint32_t(j.A)));
         }
+        if (!on_host[i])
+            g_enc_variant[enc_variant(j.o1, j.nx, uint32_t(j.A))].fetch_add(1, std::memory_order_relaxed);
         const uint32_t per = enc_replay_chunks(j.nx);
         for (uint32_t c0 = 0; c0 < nch; c0 += per) {
             items.push_back(uint32_t(eall.size()));
@@ -1305,6 +1308,10 @@ void Compressor::run(std::vector<CompressReq> &reqs) {
 void rans_enc_chain_counts(uint64_t *out2) {
     out2[0] = g_enc_host.load();
     out2[1] = g_enc_gpu.load();
+}
+
+void rans_enc_variant_counts(uint64_t *enc) {
+    for (int i = 0; i < EV_COUNT; i++) enc[i] = g_enc_variant[i].load(std::memory_order_relaxed);
 }
 
 void compress_batch(GpuCtx &g, std::vector<CompressReq> &reqs) {

@@ -322,6 +322,9 @@ using host::now_ns;
 using host::step_trace;
 
 std::atomic<uint64_t> g_rans_host{0}, g_rans_gpu{0};   // fqz5_rans_chain_counts
+// fqz5_rans_variant_counts: GPU-launched jobs by dec_variant, and those of
+// them launched in more than one hedged copy
+std::atomic<uint64_t> g_dec_variant[DV_COUNT], g_dec_variant_hedged[DV_COUNT];
 
 // a chain's kind for the cost model
 inline int chain_kind(const DJ &j) { return j.o1 ? host::CK_RANS_O1 : host::CK_RANS_O0; }
@@ -503,6 +506,11 @@ void Decompressor::run_djs(const std::vector<int> &ids, bool may_host) {
         steps.push_back(double(d.n / uint32_t(d.nx)) * (d.nreg ? 1.0 : tabw));
     HedgeShare share(size_t(g_.cus));          // held until the launch is synchronised
     const std::vector<int> cp = hedge_plan(steps, share.cus);
+    for (size_t k = 0; k < djs.size(); k++) {
+        const int v = dec_variant(djs[k]);
+        g_dec_variant[v].fetch_add(1, std::memory_order_relaxed);
+        if (cp[k] > 1) g_dec_variant_hedged[v].fetch_add(1, std::memory_order_relaxed);
+    }
     if (std::any_of(cp.begin(), cp.end(), [](int c) { return c > 1; })) {
         const size_t nj = djs.size();
         uint32_t *d_done = g_.arena.alloc_n<uint32_t>(nj);
@@ -791,6 +799,21 @@ void decompress_batch(GpuCtx &g, std::vector<DecompressReq> &reqs, const host::C
 void rans_chain_counts(uint64_t *out2) {
     out2[0] = g_rans_host.load();
     out2[1] = g_rans_gpu.load();
+}
+
+void rans_variant_counts(uint64_t *dec, uint64_t *dec_hedged, uint64_t *enc, int *ndec, int *nenc) {
+    for (int i = 0; i < DV_COUNT; i++) {
+        if (dec) dec[i] = g_dec_variant[i].load(std::memory_order_relaxed);
+        if (dec_hedged) dec_hedged[i] = g_dec_variant_hedged[i].load(std::memory_order_relaxed);
+    }
+    if (enc) rans_enc_variant_counts(enc);
+    if (ndec) *ndec = DV_COUNT;
+    if (nenc) *nenc = EV_COUNT;
+}
+
+const char *rans_variant_name(int dir, int i) {
+    if (dir == 0) return i >= 0 && i < DV_COUNT ? DEC_VARIANT_NAMES[i] : nullptr;
+    return dir == 1 && i >= 0 && i < EV_COUNT ? ENC_VARIANT_NAMES[i] : nullptr;
 }
 
 }  // namespace fqz5

@@ -256,6 +256,25 @@ def rans_enc_chain_counts() -> tuple[int, int]:
     return int(c[0]), int(c[1])
 
 
+def rans_variant_counts() -> tuple[dict[str, int], dict[str, int], dict[str, int]]:
+    """fqz5_rans_variant_counts: GPU-launched rANS chain jobs so far by the
+    kernel body that ran them, as (decoder, decoder jobs launched in several
+    hedged copies, encoder), each keyed by fqz5_rans_variant_name."""
+    so = load()
+    so.fqz5_rans_variant_counts.restype = None
+    so.fqz5_rans_variant_counts.argtypes = [C.POINTER(C.c_uint64)] * 3 + [C.POINTER(C.c_int)] * 2
+    so.fqz5_rans_variant_name.restype = C.c_char_p
+    so.fqz5_rans_variant_name.argtypes = [C.c_int, C.c_int]
+    nd, ne = C.c_int(0), C.c_int(0)
+    so.fqz5_rans_variant_counts(None, None, None, C.byref(nd), C.byref(ne))
+    dec, hed, enc = (C.c_uint64 * nd.value)(), (C.c_uint64 * nd.value)(), (C.c_uint64 * ne.value)()
+    so.fqz5_rans_variant_counts(dec, hed, enc, None, None)
+    dn = [so.fqz5_rans_variant_name(0, i).decode() for i in range(nd.value)]
+    en = [so.fqz5_rans_variant_name(1, i).decode() for i in range(ne.value)]
+    return ({k: int(v) for k, v in zip(dn, dec)}, {k: int(v) for k, v in zip(dn, hed)},
+            {k: int(v) for k, v in zip(en, enc)})
+
+
 def rans_enc_chain_host(data: bytes, order: int, bits: int, freq) -> list[int] | None:
     """fqz5_rans_enc_chain_host: the bare encoder chain's checkpoints (u32
     words) on a host core (no GPU).  freq: 256 frequencies (order 0) or

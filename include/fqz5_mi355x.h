@@ -207,6 +207,15 @@ int fqz5_unlzp_host(const unsigned char *in, size_t in_len, unsigned char *out, 
 int fqz5_set_host_encode(int mode);
 /* Encoder chains placed so far: out2[0] on host cores, out2[1] on the GPU. */
 void fqz5_rans_enc_chain_counts(uint64_t *out2);
+/* GPU-launched rANS chain jobs so far, by the kernel body that ran them: the
+ * decoder's bodies of k_rans_dec (dec[], and dec_hedged[] for the jobs among
+ * them launched in more than one hedged copy) and the encoder's chain kernels
+ * (enc[]).  Call once with null arrays for the lengths *ndec / *nenc, then
+ * with arrays that long; fqz5_rans_variant_name(0, i) names dec[i] and
+ * (1, i) names enc[i] (NULL past the end). */
+void fqz5_rans_variant_counts(uint64_t *dec, uint64_t *dec_hedged, uint64_t *enc, int *ndec,
+                              int *nenc);
+const char *fqz5_rans_variant_name(int dir, int i);
 /* The bare encoder chain of `in` (n > 0 bytes) on the calling thread's host
  * core (no GPU): the checkpoints k_enc_chain / k_enc_chain2w leave in
  * EncJob::ck for the same job, (ceil(steps / 256) + 1) * 4 words of which the
