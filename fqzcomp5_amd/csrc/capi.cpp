@@ -738,6 +738,8 @@ void fqz5_fqz_dec_counts(uint64_t *out2) {
     out2[1] = fqz_dec_blocks(true);
 }
 
+int fqz5_fqz_path_counts(uint64_t *out, int n) { return fqz_path_counts(out, n); }
+
 int fqz5_set_dec_small(int on) {
     const int prev = small_decoder_on() ? 1 : 0;
     g_dec_small.store(on ? 1 : 0);

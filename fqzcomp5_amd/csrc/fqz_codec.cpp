@@ -423,6 +423,16 @@ void copy_gparams(Global &G, const fqz_gparams *gp) {
 
 }  // namespace
 
+// fqz5_fqz_path_counts: blocks (not hedged copies) per decoder variant of
+// launch_group, per fix-up kernel, relaunched with longer record lists, and
+// per encoder
+static std::atomic<uint64_t> g_path[FQZ_PATH_COUNT];
+static void path_add(int i, uint64_t n = 1) { g_path[i].fetch_add(n, std::memory_order_relaxed); }
+int fqz_path_counts(uint64_t *out, int n) {
+    for (int i = 0; i < n && i < FQZ_PATH_COUNT; i++) out[i] = g_path[i].load(std::memory_order_relaxed);
+    return FQZ_PATH_COUNT;
+}
+
 // Coder output bytes P (before the 5 flush bytes) from the events' entropy
 // sum H = sum log2(total / freq) and slack S = sum -log2(1 - total 2^-24):
 // 8 P >= H - 8 (the final range over the initial one is at least 2^-8) and
@@ -547,6 +557,24 @@ void fqz_encode_prepare(GpuCtx &g, std::vector<FqzEncReq> &reqs) {
         E.g = g.upload(&dg, 1);
         E.q = R.d_in;
         E.n = n;
+        if ((G.gflags & GF_REV) && nrec > 0) {
+            // the records as the reference's reversal walks them: the last
+            // one takes the rest of the buffer (fqzcomp_qual.c:1089-1108)
+            std::vector<uint64_t> fs;
+            std::vector<uint32_t> fln;
+            size_t i = 0;
+            for (int r = 0; r < nrec && i < n; r++) {
+                const size_t len = r < nrec - 1 ? std::min<size_t>(R.lens[r], n - i) : n - i;
+                if ((R.flags[r] & F_REVERSE) && len > 1) fs.push_back(i), fln.push_back(uint32_t(len));
+                i += len;
+            }
+            if (!fs.empty()) {
+                uint8_t *fq = g.arena.alloc_n<uint8_t>(n);
+                FQZ5_HIP(hipMemcpyAsync(fq, R.d_in, n, hipMemcpyDeviceToDevice, g.stream));
+                FQZ5_HIP(launch_fqz_flip(fq, g.upload(fs), g.upload(fln), uint32_t(fs.size()), g.stream));
+                E.q = fq;
+            }
+        }
         std::vector<uint32_t> lens(R.lens, R.lens + std::max(nrec, 0));
         std::vector<uint32_t> sels(size_t(std::max(nrec, 0))), fl(size_t(std::max(nrec, 0)));
         for (int r = 0; r < nrec; r++) {
@@ -577,6 +605,7 @@ void fqz_encode_prepare(GpuCtx &g, std::vector<FqzEncReq> &reqs) {
         // reproduces).
         W.parallel = G.nparam == 1 && !(G.gflags & GF_MULTI) && nrec > 0;
         for (int r = 0; W.parallel && r < nrec; r++) W.parallel = R.lens[r] > 0;
+        path_add(W.parallel ? FQZ_PATH_ENC_PARALLEL : FQZ_PATH_ENC_SERIAL);
         if (!W.parallel) {
             E.models = g.fqz_tmp.alloc_n<uint8_t>(size_t(FQZ_CTX) * FQZ_QMODEL_BYTES);
             FQZ5_HIP(launch_fqz_model_init(E.models, G.max_sym + 1, g.stream));
@@ -913,9 +942,12 @@ bool small_sets_ok(uint32_t ns) {
 
 void dec_lists(GpuCtx &g, FqzDecReq::Work &W) {
     FqzDecJob &D = W.D;
-    D.cap_list = (W.dedup || W.rev || W.map_mode == 2) ? std::min<uint32_t>(W.cap, W.total + 1) : 0;
+    // (with several parameter blocks the decoders list every coded record,
+    // whether or not a qmap will be applied to it)
+    const bool recs = W.G.nparam > 1;
+    D.cap_list = (W.dedup || W.rev || recs) ? std::min<uint32_t>(W.cap, W.total + 1) : 0;
     const size_t c = std::max<uint32_t>(D.cap_list, 1);
-    D.recs = g.arena.alloc_n<uint4>(W.map_mode == 2 ? c : 1);
+    D.recs = g.arena.alloc_n<uint4>(recs ? c : 1);
     D.dups = g.arena.alloc_n<uint2>(W.dedup ? c : 1);
     D.revs = g.arena.alloc_n<uint2>(W.rev ? c : 1);
 }
@@ -1072,6 +1104,7 @@ void fqz_decode_batch(GpuCtx &g, std::vector<FqzDecReq> &reqs) {
                     FQZ5_HIP(launch_fqz_small_back(js[k].back, live_syms[k], g.stream));
             if (!js.empty()) {
                 g_dec_blocks[smallv ? 1 : 0] += nj;
+                path_add(FQZ_PATH_DEC + var, nj);
                 EventPair ev(prof_on(), g.stream);
                 if (smallv)
                     FQZ5_HIP(launch_fqz_dec_small(g.upload(js), int(js.size()), dtv != 0, g.stream));
@@ -1090,6 +1123,9 @@ void fqz_decode_batch(GpuCtx &g, std::vector<FqzDecReq> &reqs) {
         for (FqzDecReq *R : rs) {
             FqzDecReq::Work &W = *R->w;
             FQZ5_HIP(launch_fqz_dec_fix(W.D, W.map_mode, W.dedup, W.rev, g.stream));
+            if (W.map_mode) path_add(W.map_mode == 2 ? FQZ_PATH_MAP_RECS : FQZ_PATH_MAP_ALL);
+            if (W.dedup) path_add(FQZ_PATH_DUPS);
+            if (W.rev) path_add(FQZ_PATH_REVS);
             g.download(&W.st, W.D.status, 1);
         }
         g.sync();
@@ -1100,6 +1136,10 @@ void fqz_decode_batch(GpuCtx &g, std::vector<FqzDecReq> &reqs) {
         if (R->w->st == -2) {
             R->w->cap = R->w->total + 1;
             dec_lists(g, *R->w);
+            // the aborted launch marked the models it wrote to back_hi; the
+            // second starts from fresh models again
+            if (R->w->D.hi_bits) g.memset0(R->w->D.hi_bits, FQZ_CTX / 8);
+            path_add(FQZ_PATH_RELAUNCH);
             again.push_back(R);
         }
     if (!again.empty()) launch_group(again);

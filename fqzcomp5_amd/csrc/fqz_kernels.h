@@ -202,6 +202,9 @@ hipError_t launch_fqz_records(const FqzStatJob &j, hipStream_t s);
 hipError_t launch_fqz_hist(const FqzStatJob &j, int nchunks, int mode, hipStream_t s);
 hipError_t launch_fqz_model_init(uint8_t *models, int live, hipStream_t s);
 hipError_t launch_fqz_encode(const FqzEncJob &j, hipStream_t s);
+// reverses q[start[k] .. start[k] + len[k]) for k < nflip (GFLAG_DO_REV)
+hipError_t launch_fqz_flip(uint8_t *q, const uint64_t *start, const uint32_t *len, uint32_t nflip,
+                           hipStream_t s);
 // fqz_decode.hip: ne = lane registers per model (live + 2 <= 64 ? 1 : 2),
 // seq = sequence bases in the context, qid = one qtab shared by every
 // parameter block (its values ride in the cached models); map_mode 0 none / 1 one qmap / 2 per record

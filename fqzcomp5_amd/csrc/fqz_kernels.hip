@@ -177,6 +177,25 @@ DEV uint32_t next_ctx(const FqzDevParam &pm, Ctx &st, uint32_t q, uint32_t base)
 }
 
 // --------------------------------------------------------------------------
+// GFLAG_DO_REV: the reference reverses the flagged records of its input
+// before it codes them (fqzcomp_qual.c:1086-1110), so the duplicate test and
+// every context see the flipped bytes.  Here the encoders read a copy of the
+// block whose flagged records (start[k], len[k]) this kernel reverses.
+// --------------------------------------------------------------------------
+__global__ void k_fqz_flip(uint8_t *q, const uint64_t *start, const uint32_t *len, uint32_t nflip) {
+    for (uint32_t r = blockIdx.x; r < nflip; r += gridDim.x) {
+        uint8_t *o = q + start[r];
+        const uint32_t L = len[r];
+        for (uint32_t a = threadIdx.x; a < L / 2; a += blockDim.x) {
+            const uint32_t b = L - 1 - a;
+            const uint8_t t = o[a];
+            o[a] = o[b];
+            o[b] = t;
+        }
+    }
+}
+
+// --------------------------------------------------------------------------
 // encoder (compress_block_fqz2f, fqzcomp_qual.c:1112-1208)
 // --------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void k_fqz_encode(FqzEncJob J) {
@@ -1127,6 +1146,13 @@ hipError_t launch_fqz_hist(const FqzStatJob &j, int nchunks, int mode, hipStream
 
 hipError_t launch_fqz_model_init(uint8_t *models, int live, hipStream_t s) {
     hipLaunchKernelGGL(k_fqz_model_init, dim3(FQZ_CTX / 256), dim3(256), 0, s, models, live);
+    return hipGetLastError();
+}
+
+hipError_t launch_fqz_flip(uint8_t *q, const uint64_t *start, const uint32_t *len, uint32_t nflip,
+                           hipStream_t s) {
+    if (nflip)
+        hipLaunchKernelGGL(k_fqz_flip, dim3(nflip < 4096u ? nflip : 4096u), dim3(64), 0, s, q, start, len, nflip);
     return hipGetLastError();
 }
 

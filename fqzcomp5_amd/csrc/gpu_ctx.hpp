@@ -534,6 +534,13 @@ int host_decode_mode();
 int host_encode_mode();
 // quality blocks decoded by the general (false) / small (true) fqz decoder
 uint64_t fqz_dec_blocks(bool small);
+// fqz5_fqz_path_counts: blocks per fqz decoder variant (launch_group's var,
+// 0..9), fix-up kernel, relaunch and encoder
+enum : int {
+    FQZ_PATH_DEC = 0, FQZ_PATH_MAP_ALL = 10, FQZ_PATH_MAP_RECS, FQZ_PATH_DUPS, FQZ_PATH_REVS,
+    FQZ_PATH_RELAUNCH, FQZ_PATH_ENC_SERIAL, FQZ_PATH_ENC_PARALLEL, FQZ_PATH_COUNT
+};
+int fqz_path_counts(uint64_t *out, int n);
 int small_copies();   // hedged copies of a small-decoder block
 // Copies of each of `jobs` chains: up to 4 while they fit one per CU.
 inline size_t hedge_copies(size_t jobs, size_t cus) {

@@ -41,6 +41,64 @@ class FqzSlice(C.Structure):
                 ("seq", C.POINTER(C.c_void_p))]
 
 
+class FqzParam(C.Structure):
+    """fqz_param (include/fqz5_mi355x.h; htscodecs fqzcomp_qual.h:92-125)."""
+    _fields_ = [("context", C.c_uint16), ("pflags", C.c_uint),
+                ("do_sel", C.c_uint), ("do_dedup", C.c_uint),
+                ("store_qmap", C.c_uint), ("fixed_len", C.c_uint),
+                ("use_qtab", C.c_ubyte), ("use_dtab", C.c_ubyte), ("use_ptab", C.c_ubyte),
+                ("qbits", C.c_uint), ("qloc", C.c_uint),
+                ("pbits", C.c_uint), ("ploc", C.c_uint),
+                ("dbits", C.c_uint), ("dloc", C.c_uint),
+                ("sbits", C.c_uint), ("sloc", C.c_uint),
+                ("bbits", C.c_uint), ("bloc", C.c_uint), ("boff", C.c_uint),
+                ("max_sym", C.c_int), ("nsym", C.c_int), ("max_sel", C.c_int),
+                ("qmap", C.c_uint * 256), ("qtab", C.c_uint * 256),
+                ("ptab", C.c_uint * 1024), ("dtab", C.c_uint * 256),
+                ("qshift", C.c_int), ("pshift", C.c_int), ("dshift", C.c_int),
+                ("sshift", C.c_int), ("qmask", C.c_uint),
+                ("do_r2", C.c_int), ("do_qa", C.c_int)]
+
+
+class FqzGParams(C.Structure):
+    """fqz_gparams (include/fqz5_mi355x.h; fqzcomp_qual.h:129-139)."""
+    _fields_ = [("vers", C.c_int), ("gflags", C.c_uint), ("nparam", C.c_int),
+                ("max_sel", C.c_int), ("stab", C.c_uint * 256), ("max_sym", C.c_int),
+                ("p", C.POINTER(FqzParam))]
+
+
+def fqz_gparams(gflags: int, params: list[dict], max_sel: int = 0, stab=None,
+                max_sym: int | None = None, vers: int = 5) -> FqzGParams:
+    """A caller's fqz_gparams from plain values: one dict per parameter block,
+    keyed by the fqz_param field names (tables as sequences, missing fields
+    zero).  The blocks stay alive with the returned structure."""
+    blocks = (FqzParam * len(params))()
+    for b, d in zip(blocks, params):
+        for k, v in d.items():
+            if k in ("qmap", "qtab", "ptab", "dtab"):
+                arr = getattr(b, k)
+                for i, x in enumerate(v):
+                    arr[i] = int(x)
+            else:
+                setattr(b, k, int(v))
+    gp = FqzGParams(vers, gflags, len(params), max_sel)
+    for i, x in enumerate(stab if stab is not None else []):
+        gp.stab[i] = int(x)
+    gp.max_sym = max(b.max_sym for b in blocks) if max_sym is None else max_sym
+    gp.p = C.cast(blocks, C.POINTER(FqzParam))
+    gp._blocks = blocks
+    return gp
+
+
+def fqz_gparams_state(gp: FqzGParams) -> dict:
+    """What fqz_compress leaves in a caller's block: gflags, and per parameter
+    block the sequence-context bits and the (shifted) position / delta tables."""
+    return {"gflags": int(gp.gflags),
+            "blocks": [{"bbits": int(gp.p[k].bbits), "bloc": int(gp.p[k].bloc),
+                        "ptab": list(gp.p[k].ptab), "dtab": list(gp.p[k].dtab)}
+                       for k in range(gp.nparam)]}
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -275,6 +333,28 @@ def rans_variant_counts() -> tuple[dict[str, int], dict[str, int], dict[str, int
             {k: int(v) for k, v in zip(en, enc)})
 
 
+FQZ_PATH_NAMES = (["dec_ne%d_%s_%s" % (1 + (v >> 2), "seq" if v & 2 else "noseq",
+                                       "qid" if v & 1 else "qtab") for v in range(8)] +
+                  ["dec_small", "dec_small_dt", "map_all", "map_recs", "dups", "revs",
+                   "relaunched", "enc_serial"])
+
+
+def fqz_path_counts() -> dict[str, int]:
+    """fqz5_fqz_path_counts: fqz blocks so far per decoder variant (the general
+    decoder by model registers, sequence context and shared qtab; the small
+    one without and with delta terms), per fix-up kernel, relaunched with
+    longer record lists, and encoded by the serial kernel; "enc_parallel" the
+    blocks the parallel encoder took."""
+    so = load()
+    so.fqz5_fqz_path_counts.restype = C.c_int
+    so.fqz5_fqz_path_counts.argtypes = [C.POINTER(C.c_uint64), C.c_int]
+    names = FQZ_PATH_NAMES + ["enc_parallel"]
+    out = (C.c_uint64 * len(names))()
+    if so.fqz5_fqz_path_counts(out, len(names)) != len(names):
+        raise NativeError("fqz5_fqz_path_counts: the library counts other paths")
+    return {k: int(v) for k, v in zip(names, out)}
+
+
 def rans_enc_chain_host(data: bytes, order: int, bits: int, freq) -> list[int] | None:
     """fqz5_rans_enc_chain_host: the bare encoder chain's checkpoints (u32
     words) on a host core (no GPU).  freq: 256 frequencies (order 0) or
@@ -407,11 +487,13 @@ def _fqz_slice(lens, flags, seq: bytes | None):
 
 
 def fqz_compress(qual: bytes, lens, flags, strat: int, seq: bytes | None = None,
-                 vers: int = 4) -> bytes:
-    """fqz_compress on the GPU (host buffers; values are q-33)."""
+                 vers: int = 4, gp: FqzGParams | None = None) -> bytes:
+    """fqz_compress on the GPU (host buffers; values are q-33).  gp: the
+    caller's parameters (fqz_gparams()), edited in place as the reference does."""
     s, keep, _, _ = _fqz_slice(lens, flags, seq)
     n = C.c_size_t(0)
-    p = load().fqz_compress(vers, C.byref(s), bytes(qual), len(qual), C.byref(n), strat, None)
+    p = load().fqz_compress(vers, C.byref(s), bytes(qual), len(qual), C.byref(n), strat,
+                            C.byref(gp) if gp is not None else None)
     if not p:
         raise NativeError("fqz_compress failed: " + last_error())
     out = C.string_at(p, n.value)

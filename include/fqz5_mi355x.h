@@ -111,8 +111,9 @@ typedef struct {
  * s->flags[] as selectors while running (cleared on return).  gp == NULL
  * picks parameters from the data (strat 0..4); a caller-supplied gp is used
  * as is (and, as in the reference, its position / delta tables are
- * shifted in place).  Returns a malloc()ed stream (caller frees), NULL on
- * failure. */
+ * shifted in place), up to 4 parameter blocks: more fail here and in
+ * fqz_decompress (fqz5_fqz_decompress_host reads such a stream).  Returns
+ * a malloc()ed stream (caller frees), NULL on failure. */
 char *fqz_compress(int vers, fqz_slice *s, char *in, size_t in_size,
                    size_t *out_size, int strat, fqz_gparams *gp);
 
@@ -401,6 +402,16 @@ int fqz5_set_dec_small(int on);
 /* Quality blocks decoded since the library was loaded: out2[0] by the
  * general fqz decoder, out2[1] by the small-alphabet one. */
 void fqz5_fqz_dec_counts(uint64_t *out2);
+/* fqz quality blocks (not hedged copies) since the library was loaded, by
+ * the code that took them: out[0..9] launched per decoder variant (0..7 the
+ * general decoder, index 4 (two model registers) + 2 (sequence context) +
+ * 1 (one qtab shared by the parameter blocks); 8 and 9 the small decoder
+ * without and with delta terms), out[10..13] given to the fix-up kernels
+ * (qmap over the block, qmap per record, duplicates, reversals), out[14]
+ * launched a second time with longer record lists, out[15] encoded by the
+ * serial encoder and out[16] by the parallel one.  Fills min(n, 17)
+ * entries and returns 17. */
+int fqz5_fqz_path_counts(uint64_t *out, int n);
 
 /* Device check of the fqz decoder's division: floor(n / t) computed as
  * (u32)fma(n, recip(t), 2^-19) for every t < 2^16 and ~2000 n each.

@@ -26,6 +26,11 @@ _libc = C.CDLL(None)
 _libc.free.argtypes = [C.c_void_p]
 
 
+# the caller's parameter structures (one definition, the product binding's)
+from fqzcomp5_amd.lib import (FqzGParams, FqzParam, fqz_gparams,  # noqa: E402,F401
+                              fqz_gparams_state)
+
+
 class FqzSlice(C.Structure):
     # htscodecs/fqzcomp_qual.h:59-64 (fork ABI)
     _fields_ = [("num_records", C.c_int),
@@ -148,8 +153,10 @@ class _Codec:
     def _slice(self, lens, flags, seq: bytes | None):
         import numpy as np
         nr = len(lens)
-        L = (C.c_uint32 * nr)(*[int(x) for x in lens])
-        Fl = (C.c_uint32 * nr)(*[int(x) for x in flags])
+        # (one zeroed entry past the end: with no records the reference still
+        # reads len[0], fqzcomp_qual.c:1134)
+        L = (C.c_uint32 * (nr + 1))(*[int(x) for x in lens])
+        Fl = (C.c_uint32 * (nr + 1))(*[int(x) for x in flags])
         keep = [L, Fl]
         S = None
         if seq is not None:
@@ -163,11 +170,22 @@ class _Codec:
         return s, keep
 
     def fqz_compress(self, qual: bytes, lens, flags, strat: int,
-                     seq: bytes | None = None, vers: int = 4) -> bytes:
+                     seq: bytes | None = None, vers: int = 4,
+                     gp: FqzGParams | None = None) -> bytes:
+        """gp: the caller's parameters (fqz_gparams()); the call edits the
+        block in place, fqz_gparams_state(gp) reads what it left.  The
+        selector bits a caller sets in flags >> 16 reach the codec; the
+        array handed in is not written."""
         s, keep = self._slice(lens, flags, seq)
         n = C.c_size_t(0)
-        p = self._fc(vers, C.byref(s), bytes(qual), len(qual), C.byref(n),
-                     strat, None)
+        # a private copy: reversal (GFLAG_DO_REV) flips the records in place
+        buf = C.create_string_buffer(bytes(qual), max(len(qual), 1))
+        p = self._fc(vers, C.byref(s), buf, len(qual), C.byref(n), strat,
+                     C.byref(gp) if gp is not None else None)
+        assert buf.raw[:len(qual)] == bytes(qual), "input not restored"
+        nr = len(lens)
+        self.last_lens = [int(x) for x in keep[0]][:nr]      # as the call left them
+        self.last_flags = [int(x) for x in keep[1]][:nr]
         return self._take(p, n.value)
 
     def fqz_decompress(self, comp: bytes, lens, flags,

@@ -517,14 +517,79 @@ static void flip_records(uint8_t *q, size_t n, int nrec, const uint32_t *lens,
     }
 }
 
+/* The caller's parameter blocks, laid out as include/fqz5_mi355x.h
+ * (fqzcomp_qual.h:92-139). */
+typedef struct {
+    uint16_t context;
+    unsigned int pflags;
+    unsigned int do_sel, do_dedup, store_qmap, fixed_len;
+    unsigned char use_qtab, use_dtab, use_ptab;
+    unsigned int qbits, qloc;
+    unsigned int pbits, ploc;
+    unsigned int dbits, dloc;
+    unsigned int sbits, sloc;
+    unsigned int bbits, bloc, boff;
+    int max_sym, nsym, max_sel;
+    unsigned int qmap[256];
+    unsigned int qtab[256];
+    unsigned int ptab[1024];
+    unsigned int dtab[256];
+    int qshift, pshift, dshift, sshift;
+    unsigned int qmask;
+    int do_r2, do_qa;
+} ora_fqz_param;
+
+typedef struct {
+    int vers;
+    unsigned int gflags;
+    int nparam;
+    int max_sel;
+    unsigned int stab[256];
+    int max_sym;
+    ora_fqz_param *p;
+} ora_fqz_gparams;
+
+/* Caller-supplied parameters, used as they are (fqzcomp_qual.c:1040-1045). */
+static int take_params(fglobal *g, const ora_fqz_gparams *gp) {
+    memset(g, 0, sizeof *g);
+    g->vers = gp->vers;
+    g->gflags = gp->gflags;
+    g->nparam = gp->nparam;
+    g->max_sel = gp->max_sel;
+    g->max_sym = gp->max_sym;
+    memcpy(g->stab, gp->stab, sizeof g->stab);
+    if (gp->nparam <= 0 || !(g->p = calloc((size_t)gp->nparam, sizeof(fparam)))) return -1;
+    for (int k = 0; k < gp->nparam; k++) {
+        const ora_fqz_param *a = &gp->p[k];
+        fparam *b = &g->p[k];
+        b->ctx0 = a->context;
+        b->pflags = a->pflags;
+        b->sel = (int)a->do_sel, b->dedup = (int)a->do_dedup;
+        b->qmap_stored = (int)a->store_qmap, b->fixed = (int)a->fixed_len;
+        b->qtab_on = a->use_qtab, b->dtab_on = a->use_dtab, b->ptab_on = a->use_ptab;
+        b->qbits = a->qbits, b->qloc = a->qloc, b->pbits = a->pbits, b->ploc = a->ploc;
+        b->dbits = a->dbits, b->dloc = a->dloc, b->sloc = a->sloc;
+        b->bbits = a->bbits, b->bloc = a->bloc, b->boff = a->boff;
+        b->max_sym = a->max_sym, b->nsym = a->nsym, b->max_sel = a->max_sel;
+        memcpy(b->qmap, a->qmap, sizeof b->qmap);
+        memcpy(b->qtab, a->qtab, sizeof b->qtab);
+        memcpy(b->ptab, a->ptab, sizeof b->ptab);
+        memcpy(b->dtab, a->dtab, sizeof b->dtab);
+        b->qshift = a->qshift, b->pshift = a->pshift, b->dshift = a->dshift;
+        b->qmask = a->qmask;
+    }
+    return 0;
+}
+
 uint8_t *ora_fqz_compress(int vers, ora_fqz_slice *s, uint8_t *q, size_t n,
-                          size_t *out_size, int strat, void *gp_unused) {
-    (void)gp_unused;
+                          size_t *out_size, int strat, void *gp_in) {
+    ora_fqz_gparams *gp = gp_in;
     size_t cap = (size_t)(n * 1.1 + 100000);
     uint8_t *out = malloc(cap);
     if (!out) return NULL;
     fglobal g;
-    if (pick_params(&g, vers, strat, s->num_records, s->len, s->flags, q, n) < 0) {
+    if ((gp ? take_params(&g, gp)
+            : pick_params(&g, vers, strat, s->num_records, s->len, s->flags, q, n)) < 0) {
         free(out);
         return NULL;
     }
@@ -534,6 +599,15 @@ uint8_t *ora_fqz_compress(int vers, ora_fqz_slice *s, uint8_t *q, size_t n,
     } else {
         for (int k = 0; k < g.nparam; k++)
             if (g.p[k].bbits) g.gflags |= GF_SEQ;
+    }
+    if (gp) {   /* the reference works in the caller's block (:1047-1076) */
+        gp->gflags = g.gflags;
+        for (int k = 0; k < g.nparam; k++) {
+            gp->p[k].bbits = g.p[k].bbits;
+            gp->p[k].bloc = g.p[k].bloc;
+            for (int i = 0; i < 1024; i++) gp->p[k].ptab[i] <<= gp->p[k].ploc;
+            for (int i = 0; i < 256; i++) gp->p[k].dtab[i] <<= gp->p[k].dloc;
+        }
     }
     int hdr = ora_var_put_u32(out, out + cap, (uint32_t)n);
     hdr += put_params(&g, out + hdr);
