@@ -201,6 +201,26 @@ NmDev device_copy(fqz5_name_table &T) {
 }
 
 }  // namespace
+
+uint32_t nm_compact(GpuCtx &g, const uint32_t *hit, uint32_t n, int pairs, uint32_t *d_rec,
+                    uint32_t *d_query) {
+    uint32_t *flag = g.arena.alloc_n<uint32_t>(size_t(n) + 1);
+    uint32_t *pos = g.arena.alloc_n<uint32_t>(size_t(n) + 1);
+    hipLaunchKernelGGL(k_nm_flag, dim3(n / 256 + 1), dim3(256), 0, g.stream, hit, n, pairs, flag);
+    FQZ5_HIP(hipGetLastError());
+    size_t tb = 0;
+    FQZ5_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, flag, pos, int(n + 1), g.stream));
+    void *tmp = g.arena.alloc_n<uint8_t>(tb ? tb : 1);
+    FQZ5_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tb, flag, pos, int(n + 1), g.stream));
+    hipLaunchKernelGGL(k_nm_scatter, dim3(n / 256 + 1), dim3(256), 0, g.stream, flag, pos, hit, n,
+                       d_rec, d_query);
+    FQZ5_HIP(hipGetLastError());
+    uint32_t cnt = 0;
+    g.download(&cnt, pos + n, 1);
+    g.sync();
+    return cnt;
+}
+
 }  // namespace fqz5
 
 using namespace fqz5;
@@ -291,23 +311,10 @@ int fqz5_names_match(const fqz5_name_table *T, const uint8_t *d_names, uint64_t 
         if (nz < nrec) throw GpuError("names_match: fewer names than records");
         const uint32_t n = uint32_t(nrec);
         uint32_t *hit = g.arena.alloc_n<uint32_t>(n);
-        uint32_t *flag = g.arena.alloc_n<uint32_t>(size_t(n) + 1);
-        uint32_t *pos = g.arena.alloc_n<uint32_t>(size_t(n) + 1);
         hipLaunchKernelGGL(k_name_match, dim3((n + 63) / 64), dim3(64), 0, g.stream, d_names, name_len,
                            z, n, whole, D, hit);
         FQZ5_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_nm_flag, dim3(n / 256 + 1), dim3(256), 0, g.stream, hit, n, pairs, flag);
-        FQZ5_HIP(hipGetLastError());
-        size_t tb = 0;
-        FQZ5_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, flag, pos, int(n + 1), g.stream));
-        void *tmp = g.arena.alloc_n<uint8_t>(tb ? tb : 1);
-        FQZ5_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tb, flag, pos, int(n + 1), g.stream));
-        hipLaunchKernelGGL(k_nm_scatter, dim3(n / 256 + 1), dim3(256), 0, g.stream, flag, pos, hit, n,
-                           d_rec, d_query);
-        FQZ5_HIP(hipGetLastError());
-        uint32_t cnt = 0;
-        g.download(&cnt, pos + n, 1);
-        g.sync();
+        const uint32_t cnt = nm_compact(g, hit, n, pairs, d_rec, d_query);
         *n_hit = cnt;
         g.reset();
         return 0;

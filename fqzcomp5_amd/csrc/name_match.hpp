@@ -38,4 +38,14 @@ __host__ __device__ inline uint64_t nm_slot(uint32_t tag, uint32_t query) {
     return uint64_t(query) << 32 | tag;
 }
 
+struct GpuCtx;
+
+// name_match.hip: the compaction both matchers end with.  hit[0..n) holds
+// per record a query index or NM_NONE; the records to report (a hit, or with
+// pairs the mate of one) go, ascending, into d_rec with their hit[] value in
+// d_query (a flag kernel, an exclusive scan, a scatter).  Returns their number
+// after synchronising g's stream; scratch comes from g's arena.
+uint32_t nm_compact(GpuCtx &g, const uint32_t *hit, uint32_t n, int pairs, uint32_t *d_rec,
+                    uint32_t *d_query);
+
 }  // namespace fqz5

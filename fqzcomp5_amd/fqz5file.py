@@ -30,6 +30,13 @@ fqzcomp5 writes, produced and read by this library alone.
                                      quality decoded for the blocks with hits
                                      only -> fqz5_fastq_format_list (the hit
                                      records' text, in file order)
+    find_seqs(src, patterns) / extract_seqs_file(src, dst, patterns[, dst2=]) /
+    extract_seqs_bytes: records by sequence content, the same pass with the
+                                     sequence section as the key: decoded for
+                                     every block and scanned on the device for
+                                     the patterns (fqz5_seqs_match) -> names
+                                     and quality decoded for the blocks with
+                                     hits only -> fqz5_fastq_format_list
 
 File layout (fqzcomp5.c:2563-2630, :2959-2969): "FQZ5\\1\\1\\0\\0", u64 index
 offset, the blocks, then "FQZ5IDX\\0", u32 nblocks and per block {u64 file
@@ -121,6 +128,21 @@ def _load():
         so.fqz5_names_match.restype = C.c_int
         so.fqz5_names_match.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int,
                                         C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+        so.fqz5_seqs_table_build.restype = C.c_void_p
+        so.fqz5_seqs_table_build.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int]
+        so.fqz5_seqs_table_free.restype = None
+        so.fqz5_seqs_table_free.argtypes = [C.c_void_p]
+        so.fqz5_seqs_table_anchor.restype = C.c_uint32
+        so.fqz5_seqs_table_anchor.argtypes = [C.c_void_p]
+        so.fqz5_seqs_match_tile.restype = C.c_uint32
+        so.fqz5_seqs_match_tile.argtypes = []
+        so.fqz5_seqs_scan_host.restype = C.c_int
+        so.fqz5_seqs_scan_host.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p,
+                                           C.c_uint64, C.c_void_p, C.c_void_p]
+        so.fqz5_seqs_match.restype = C.c_int
+        so.fqz5_seqs_match.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                       C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
+                                       C.c_void_p]
         _bound = True
     return so
 
@@ -130,7 +152,10 @@ def _load():
 # download, write; extract_file: index, read, upload, decode, format,
 # download, write; find_names / extract_names_file: index, read, upload,
 # names (the blocks parsed and CRC-checked, their name sections decoded),
-# match, decode, format, download, write); the stages end with what the
+# match, decode, format, download, write; find_seqs / extract_seqs_file: the
+# same with seqs, the sequence sections decoded, in place of names, after
+# table, the patterns expanded and their table built, and before result, the
+# hits mapped back to the caller's patterns); the stages end with what the
 # library synchronises
 _TRACE = {}
 
@@ -2058,11 +2083,25 @@ class _NameTable:
         self.close()
 
 
-def _names_windows(rd, tab: _NameTable, whole: bool, pairs: bool, extract: bool, plus_name: bool,
-                   with_qual: bool, device: str, window_bytes: int | None):
-    """One pass over the container behind `rd` (see above), window by window:
-    (file record numbers of the window's hits, their query indices, the hits'
-    text as device tensors or None without `extract`; pairs: R1 and R2 text)."""
+def _sec_of(v, sec: int):
+    """(offset in the block, compressed size, decoded size) of a section."""
+    return {S.SEC_NAME: (v.name_off, v.name_size, v.name_ulen),
+            S.SEC_SEQ: (v.seq_off, v.seq_size, v.seq_ulen),
+            S.SEC_QUAL: (v.qual_off, v.qual_size, v.qual_ulen)}[sec]
+
+
+def _key_windows(rd, key: int, match, pairs: bool, extract: bool, plus_name: bool,
+                 with_qual: bool, device: str, window_bytes: int | None):
+    """One pass over the container behind `rd` (see above), window by window,
+    for a lookup whose key is the section `key` (SEC_NAME: by read name,
+    SEC_SEQ: by sequence content): every block is read, checked and
+    CRC-checked and its key section decoded; match(key pointer, its size, the
+    block's record lengths, hits) leaves the block's compacted hits (record
+    indices, query indices) in the device tensor `hits` and returns their
+    number; the other sections are decoded for the blocks with hits alone.
+    Yields (file record numbers of the window's hits, their query indices, the
+    hits' text as device tensors or None without `extract`; pairs: R1 and R2
+    text)."""
     import torch
     so = _load()
     with _stage("index"):
@@ -2090,29 +2129,29 @@ def _names_windows(rd, tab: _NameTable, whole: bool, pairs: bool, extract: bool,
             _check_entry(index, b, hv, a)
         with _stage("upload"):
             buf = torch.from_numpy(np.ascontiguousarray(hv)).to(device)   # blocking
-        with _stage("names"):
+        with _stage("names" if key == S.SEC_NAME else "seqs"):
             ranges = Blocks([(index[b][0] - a, index[b][1] - a) for b in grp], index.version)
             views, lens, fasta = _parse_checked(hv, buf, ranges)
-            noff = np.concatenate([[0], np.cumsum([v.name_ulen for v in views])]).astype(np.int64)
-            name_d = torch.empty(int(noff[-1]) + 1, dtype=torch.uint8, device=device)
+            koff = np.concatenate([[0], np.cumsum([_sec_of(v, key)[2]
+                                                   for v in views])]).astype(np.int64)
+            key_d = torch.empty(int(koff[-1]) + 1, dtype=torch.uint8, device=device)
             base = buf.data_ptr()
             rls = [ln.ctypes.data_as(C.POINTER(C.c_uint32)) for ln in lens]
-            secs = [S.Section(base + s + v.name_off, name_d.data_ptr() + int(noff[j]), v.name_size,
-                              v.name_ulen, 0, S.SEC_NAME, rls[j], None, len(lens[j]), None)
-                    for j, ((s, _), v) in enumerate(zip(ranges, views))]
-            if any(r.status != 0 for r in S.decode(secs)):
+            ptr = [{key: key_d.data_ptr() + int(koff[j])} for j in range(len(views))]
+
+            def section(j, sec):          # (the quality decoder reads the block's decoded bases)
+                off, size, ulen = _sec_of(views[j], sec)
+                return S.Section(base + ranges[j][0] + off, ptr[j][sec], size, ulen, 0, sec, rls[j],
+                                 None, len(lens[j]), ptr[j][S.SEC_SEQ] if sec == S.SEC_QUAL else None)
+            if any(r.status != 0 for r in S.decode([section(j, key) for j in range(len(views))])):
                 raise _lib.NativeError("section decoding failed: " + _lib.last_error())
         recs, qidx, sels = [], [], {}
         with _stage("match"):
             hits = torch.empty((2, max(max(len(ln) for ln in lens), 1)), dtype=torch.int32,
                                device=device)
             for j, (v, ln) in enumerate(zip(views, lens)):
-                n = C.c_uint64(0)
                 _lib.after_torch(device)          # (the last block's hits have been copied)
-                _check(so.fqz5_names_match(tab.p, name_d.data_ptr() + int(noff[j]), v.name_ulen,
-                                           len(ln), int(whole), int(pairs), hits[0].data_ptr(),
-                                           hits[1].data_ptr(), C.byref(n)), "fqz5_names_match")
-                n = int(n.value)
+                n = match(ptr[j][key], _sec_of(v, key)[2], ln, hits)
                 if not n:
                     continue
                 got = hits[:, :n].cpu().numpy().view(np.uint32)      # the compacted hits alone
@@ -2124,33 +2163,27 @@ def _names_windows(rd, tab: _NameTable, whole: bool, pairs: bool, extract: bool,
         qidx = np.concatenate(qidx) if qidx else np.zeros(0, np.uint32)
         if not extract:
             yield recs, qidx, None
-            del buf, hv, name_d
+            del buf, hv, key_d
             continue
         with _stage("decode"):
-            soff, o = {}, 0
+            rest, o = [], 0
             for j in sels:
-                soff[j] = o
-                o += 2 * views[j].seq_ulen
+                for sec in (S.SEC_NAME, S.SEC_SEQ, S.SEC_QUAL):
+                    if sec == key or (sec == S.SEC_QUAL and (fasta[j] or not with_qual)):
+                        continue
+                    rest.append((j, sec, o))
+                    o += _sec_of(views[j], sec)[2]
             out_d = torch.empty(o + 1, dtype=torch.uint8, device=device)
-            secs = []
-            for j in sels:
-                (s, _), v = ranges[j], views[j]
-                sp = out_d.data_ptr() + soff[j]
-                secs.append(S.Section(base + s + v.seq_off, sp, v.seq_size, v.seq_ulen, 0,
-                                      S.SEC_SEQ, rls[j], None, len(lens[j]), None))
-                if with_qual and not fasta[j]:
-                    secs.append(S.Section(base + s + v.qual_off, sp + v.seq_ulen, v.qual_size,
-                                          v.qual_ulen, 0, S.SEC_QUAL, rls[j], None, len(lens[j]),
-                                          sp))
-            if secs and any(r.status != 0 for r in S.decode(secs)):
+            for j, sec, at in rest:
+                ptr[j][sec] = out_d.data_ptr() + at
+            if rest and any(r.status != 0 for r in S.decode([section(j, sec) for j, sec, _ in rest])):
                 raise _lib.NativeError("section decoding failed: " + _lib.last_error())
         with _stage("format"):
             def fmt(j, out, cap):
-                v, sp = views[j], out_d.data_ptr() + soff[j]
                 size, s1 = C.c_uint64(0), C.c_uint64(0)
                 _check(so.fqz5_fastq_format_list(
-                    name_d.data_ptr() + int(noff[j]), v.name_ulen, sp,
-                    sp + v.seq_ulen if with_qual and not fasta[j] else None, lens[j].ctypes.data,
+                    ptr[j][S.SEC_NAME], views[j].name_ulen, ptr[j][S.SEC_SEQ],
+                    ptr[j].get(S.SEC_QUAL), lens[j].ctypes.data,
                     len(lens[j]), sels[j].data_ptr(), int(sels[j].numel()), int(plus_name),
                     int(pairs), out, cap, C.byref(size), C.byref(s1)), "fqz5_fastq_format_list")
                 return int(size.value), int(s1.value)
@@ -2170,31 +2203,46 @@ def _names_windows(rd, tab: _NameTable, whole: bool, pairs: bool, extract: bool,
         else:
             cat = lambda rs: torch.cat([text[x:y] for x, y in rs]) if rs else text[:0]
             yield recs, qidx, (cat(r1), cat(r2))
-        del buf, hv, name_d, out_d, text
+        del buf, hv, key_d, out_d, text
+
+
+def _lookup(rd, key: int, match, pairs, extract, plus_name, with_qual, device, window_bytes, sink):
+    """_key_windows run to its end: (the hits' file record numbers, their
+    query indices, the bytes sink(windows of texts) wrote with `extract`)."""
+    recs, qidx = [], []
+
+    def windows():
+        for r, q, texts in _key_windows(rd, key, match, pairs, extract, plus_name, with_qual,
+                                        device, window_bytes):
+            recs.append(r)
+            qidx.append(q)
+            yield texts
+    if extract:
+        written = sink(windows())
+    else:
+        written = 0
+        for _ in windows():
+            pass
+    return (np.concatenate(recs) if recs else [], np.concatenate(qidx) if qidx else [], written)
 
 
 def _find(rd, names, whole, pairs, extract, plus_name, with_qual, device, window_bytes, sink):
-    """The lookup over `rd`; sink(windows of texts) consumes the hits' text
-    (extract) and returns the bytes written."""
+    """The lookup by name over `rd`; sink(windows of texts) consumes the
+    hits' text (extract) and returns the bytes written."""
     given, qs, first = _queries(names)
     if not qs:
         return _name_hits(given, first, [], [], sink(iter(())) if extract else 0)
-    recs, qidx = [], []
+    so = _load()
     with _NameTable(qs) as tab:
-        def windows():
-            for r, q, texts in _names_windows(rd, tab, whole, pairs, extract, plus_name, with_qual,
-                                              device, window_bytes):
-                recs.append(r)
-                qidx.append(q)
-                yield texts
-        if extract:
-            written = sink(windows())
-        else:
-            written = 0
-            for _ in windows():
-                pass
-    return _name_hits(given, first, np.concatenate(recs) if recs else [],
-                      np.concatenate(qidx) if qidx else [], written)
+        def match(d_key, ulen, ln, hits):
+            n = C.c_uint64(0)
+            _check(so.fqz5_names_match(tab.p, d_key, ulen, len(ln), int(whole), int(pairs),
+                                       hits[0].data_ptr(), hits[1].data_ptr(), C.byref(n)),
+                   "fqz5_names_match")
+            return int(n.value)
+        recs, qidx, written = _lookup(rd, S.SEC_NAME, match, pairs, extract, plus_name, with_qual,
+                                      device, window_bytes, sink)
+    return _name_hits(given, first, recs, qidx, written)
 
 
 def find_names(src, names, whole: bool = False, pairs: bool = False, device: str = "cuda",
@@ -2254,4 +2302,240 @@ def extract_names_file(src: str, dst: str, names, whole: bool = False, plus_name
     finally:
         rd.close()
     _trace_dump("extract_names")
+    return res
+
+
+# ---------------------------------------------------------------------------
+# Lookup by sequence content
+#
+# "The reads that contain this adapter / barcode / primer / k-mer list": the
+# pass of the lookup by name with the sequence section as the key.  Every
+# block is read once, checked against the index and CRC-checked; only its
+# SEC_SEQ section goes to the section decoder (it decodes on its own), and
+# fqz5_seqs_match (seq_match.hip) scans the bases for the patterns on the
+# device.  The extractors decode the name (and quality) sections of the
+# blocks with hits alone.  A record hits when its sequence line holds a
+# pattern as a contiguous substring, byte for byte; revcomp also searches
+# each pattern's reverse complement, which this layer expands into queries of
+# its own (the kernel knows nothing of strands).  Not built: mismatches or
+# edit distance, IUPAC expansion, case folding, the positions of occurrences,
+# several ranks, a k-mer index kept between calls.
+# ---------------------------------------------------------------------------
+class SeqHits:
+    """The result of a lookup by sequence: `records` (np.uint64) the file
+    record numbers that hold a pattern, ascending (pairs: with their mates);
+    `query` (np.int64) per record the index into the caller's patterns of the
+    first one, in list order, that occurs in it (forward before reverse
+    complement for one pattern), -1 for a mate taken only as partner;
+    `reverse` (bool) whether that occurrence is the pattern's reverse
+    complement; `missing` the caller's patterns that occur in no record (on
+    either strand with revcomp), in the caller's order; `written` the text
+    bytes written (extract_seqs_file)."""
+
+    def __init__(self, records, query, reverse, missing, written: int = 0):
+        self.records, self.query, self.reverse = records, query, reverse
+        self.missing, self.written = missing, written
+
+
+def read_pattern_list(path) -> list[bytes]:
+    """A list of patterns, one per line, line ends ('\\n', "\\r\\n") dropped and
+    empty lines skipped.  A FASTA file (its first such line starts with '>')
+    gives its sequences, the lines of a wrapped one joined."""
+    with open(path, "rb") as f:
+        lines = [x for x in (ln.rstrip(b"\r\n") for ln in f) if x]
+    if not lines or not lines[0].startswith(b">"):
+        return lines
+    out, cur = [], None
+    for ln in lines:
+        if ln.startswith(b">"):
+            if cur:
+                out.append(cur)
+            cur = b""
+        else:
+            cur += ln
+    if cur:
+        out.append(cur)
+    return out
+
+
+_COMPLEMENT = bytes.maketrans(b"ACGTacgtNn", b"TGCAtgcaNn")
+
+
+def _seq_queries(patterns, revcomp: bool):
+    """The caller's patterns as (the patterns as given, the distinct internal
+    queries, for each of those (index of the caller's pattern it first stands
+    for, whether as its reverse complement)).  The queries come in the order
+    fwd(0), rc(0), fwd(1), rc(1), ...; one equal to an earlier query is
+    dropped (a palindrome has no rc of its own).  str patterns are UTF-8; an
+    empty pattern, one with a NUL byte and, with revcomp, one with a byte
+    outside ACGTNacgtn is a ValueError."""
+    given = list(patterns)
+    qs, origin, seen = [], [], set()
+    for i, x in enumerate(given):
+        b = x.encode() if isinstance(x, str) else bytes(x)
+        if not b:
+            raise ValueError(f"pattern {i} is empty")
+        if b"\0" in b:
+            raise ValueError(f"pattern {i} holds a NUL byte")
+        forms = [(b, False)]
+        if revcomp:
+            if b.translate(None, b"ACGTacgtNn"):
+                raise ValueError(f"pattern {i} holds a byte without a complement (not ACGTN)")
+            forms.append((b.translate(_COMPLEMENT)[::-1], True))
+        for f, rev in forms:
+            if f not in seen:
+                seen.add(f)
+                qs.append(f)
+                origin.append((i, rev))
+    return given, qs, origin
+
+
+def _seq_hits(given, qs, origin, revcomp: bool, records, qidx, seen, written: int = 0) -> SeqHits:
+    """SeqHits from the matcher's output: qidx per record the index of the
+    lowest query it holds (0xFFFFFFFF: none, a mate), seen per query whether
+    it occurs in any record."""
+    records = np.asarray(records, np.uint64)
+    qidx = np.asarray(qidx, np.uint32)
+    none = qidx == 0xFFFFFFFF
+    query = np.full(len(qidx), -1, np.int64)
+    reverse = np.zeros(len(qidx), bool)
+    if len(origin):
+        at = qidx[~none].astype(np.int64)
+        query[~none] = np.asarray([i for i, _ in origin], np.int64)[at]
+        reverse[~none] = np.asarray([r for _, r in origin], bool)[at]
+    where = {q: k for k, q in enumerate(qs)}
+    missing, done = [], set()
+    for x in given:
+        b = x.encode() if isinstance(x, str) else bytes(x)
+        if b in done:
+            continue
+        done.add(b)
+        forms = [b] + ([b.translate(_COMPLEMENT)[::-1]] if revcomp else [])
+        if not any(seen[where[f]] for f in forms):
+            missing.append(x)
+    return SeqHits(records, query, reverse, missing, written)
+
+
+class _SeqTable:
+    """fqz5_seq_table of the distinct queries (freed on exit)."""
+
+    def __init__(self, queries: list[bytes], tag_bits: int = 32, anchor: int = 0):
+        self.so = _load()
+        blob = b"".join(q + b"\0" for q in queries)
+        self.p = self.so.fqz5_seqs_table_build(blob, len(blob), len(queries), tag_bits, anchor)
+        if not self.p:
+            raise _lib.NativeError("fqz5_seqs_table_build: " + _lib.last_error())
+        self.anchor = int(self.so.fqz5_seqs_table_anchor(self.p))
+
+    def scan_host(self, seq: bytes, lens, nq: int):
+        """fqz5_seqs_scan_host: (hit per record, seen per query)."""
+        lens = np.ascontiguousarray(lens, np.uint32)
+        hit = np.zeros(len(lens), np.uint32)
+        seen = np.zeros(nq, np.uint8)
+        _check(self.so.fqz5_seqs_scan_host(self.p, seq, len(seq), lens.ctypes.data, len(lens),
+                                           hit.ctypes.data, seen.ctypes.data), "fqz5_seqs_scan_host")
+        return hit, seen
+
+    def close(self) -> None:
+        if self.p:
+            self.so.fqz5_seqs_table_free(self.p)
+            self.p = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def _find_seqs(rd, patterns, revcomp, pairs, extract, plus_name, with_qual, device, window_bytes,
+               sink):
+    """The lookup by sequence over `rd`; sink(windows of texts) consumes the
+    hits' text (extract) and returns the bytes written."""
+    with _stage("table"):
+        given, qs, origin = _seq_queries(patterns, revcomp)
+    if not qs:
+        return _seq_hits(given, qs, origin, revcomp, [], [], [], sink(iter(())) if extract else 0)
+    import torch
+    so = _load()
+    with _stage("table"):
+        tab = _SeqTable(qs)
+    with tab:
+        seen = torch.zeros(len(qs), dtype=torch.uint8, device=device)
+
+        def match(d_key, ulen, ln, hits):
+            n = C.c_uint64(0)
+            _check(so.fqz5_seqs_match(tab.p, d_key, ulen, ln.ctypes.data, len(ln), int(pairs),
+                                      hits[0].data_ptr(), hits[1].data_ptr(), C.byref(n),
+                                      seen.data_ptr()), "fqz5_seqs_match")
+            return int(n.value)
+        recs, qidx, written = _lookup(rd, S.SEC_SEQ, match, pairs, extract, plus_name, with_qual,
+                                      device, window_bytes, sink)
+        seen = seen.cpu().numpy()
+    with _stage("result"):
+        return _seq_hits(given, qs, origin, revcomp, recs, qidx, seen, written)
+
+
+def find_seqs(src, patterns, revcomp: bool = False, pairs: bool = False, device: str = "cuda",
+              window_bytes: int | None = None) -> SeqHits:
+    """The records of a .fqz5 (a path, the file's bytes, or a positioned
+    reader) whose sequence holds one of `patterns` (bytes or str) as a
+    contiguous substring: every block is read, checked and CRC-checked, its
+    sequence section alone decoded and scanned on the GPU (see above); no name
+    or quality section is decoded.  Bytes are compared as they are (case
+    matters, 'N' is an ordinary byte); an occurrence never spans two records.
+    revcomp: each pattern's reverse complement (A<->T, C<->G, N; other bytes
+    are a ValueError) is searched as well.  pairs: a hit on record 2k or
+    2k + 1 selects both mates."""
+    rd, close = _reader(src)
+    try:
+        res = _find_seqs(rd, patterns, revcomp, pairs, False, False, True, device, window_bytes,
+                         None)
+    finally:
+        if close:
+            rd.close()
+    _trace_dump("find_seqs")
+    return res
+
+
+def extract_seqs_bytes(data, patterns, revcomp: bool = False, plus_name: bool = False,
+                       with_qual: bool = True, device: str = "cuda") -> bytes:
+    """The records of a .fqz5 held in memory whose sequence holds one of
+    `patterns`, in file order, as the text decompress_bytes gives for them
+    (with_qual False: FASTA text, no quality section decoded).  See
+    find_seqs."""
+    out = []
+
+    def sink(windows):
+        for (t,) in windows:
+            out.append(t.cpu().numpy().tobytes())
+        return sum(len(x) for x in out)
+    _find_seqs(_PosBytes(data), patterns, revcomp, False, True, plus_name, with_qual, device, None,
+               sink)
+    _trace_dump("extract_seqs")
+    return b"".join(out)
+
+
+def extract_seqs_file(src: str, dst: str, patterns, revcomp: bool = False, plus_name: bool = False,
+                      device: str = "cuda", dst2: str | None = None, with_qual: bool = True,
+                      window_bytes: int | None = None) -> SeqHits:
+    """The records of the .fqz5 file src whose sequence holds one of
+    `patterns` to dst, in file order: one pass over the file in windows of at
+    most `window_bytes` of compressed data; every block is read once, checked
+    against its index entry and CRC-checked, and its sequence section decoded
+    and scanned on the GPU; the name and quality sections are decoded for the
+    blocks with hits only, and the hits' text is laid out on the GPU
+    (fqz5_fastq_format_list).  dst2: the records are interleaved pairs, a hit
+    on either mate takes both, R1 records to dst and R2 records to dst2.
+    with_qual False: no quality section is decoded and the text is FASTA.  A
+    ".gz" destination is gzip-compressed.  One process; returns the SeqHits
+    (`written`: the text bytes written)."""
+    outs = [dst] + ([dst2] if dst2 is not None else [])
+    rd = _PosFile(src)
+    try:
+        res = _find_seqs(rd, patterns, revcomp, dst2 is not None, True, plus_name, with_qual,
+                         device, window_bytes, lambda w: sum(_write_texts(outs, w)))
+    finally:
+        rd.close()
+    _trace_dump("extract_seqs")
     return res

@@ -173,6 +173,54 @@ int fqz5_names_match(const fqz5_name_table *, const uint8_t *d_names, uint64_t n
                      uint64_t nrec, int whole, int pairs,
                      uint32_t *d_rec, uint32_t *d_query, uint64_t *n_hit);
 
+/* Lookup by sequence content (seq_match.hip; fqz5file.find_seqs): a table of
+ * patterns built on the host, and the records of a block's decoded bases
+ * (the records' sequences one after the other, no separators) that contain
+ * one of them as a contiguous substring.  Bytes are compared as they are
+ * (case matters, 'N' is a byte like any other); an occurrence never spans two
+ * records.  The table is keyed by the patterns' first m bytes, the anchor:
+ * the hash and slot rule of the name table, but patterns may share an anchor
+ * (separate slots of one probe, every tag match verified). */
+typedef struct fqz5_seq_table fqz5_seq_table;
+
+/* q: nq patterns, '\0' after each (as fqz5_names_table_build); tag_bits
+ * 1..32 (the file path passes 32).  anchor: 0 = min(the shortest pattern,
+ * 12), else the anchor length to use, at most 64 (tests force 1).  Refused
+ * (NULL): no pattern, an empty one, a duplicate, more than 2^20 patterns, a
+ * pattern longer than 65535 bytes, an anchor above the shortest pattern. */
+fqz5_seq_table *fqz5_seqs_table_build(const uint8_t *q, uint64_t q_len, uint64_t nq,
+                                      int tag_bits, int anchor);
+
+/* the table and its device copy (made by the first fqz5_seqs_match) */
+void fqz5_seqs_table_free(fqz5_seq_table *);
+
+/* the anchor length in use */
+uint32_t fqz5_seqs_table_anchor(const fqz5_seq_table *);
+
+/* bases per workgroup tile of the kernel */
+uint32_t fqz5_seqs_match_tile(void);
+
+/* Host restatement of the kernel's rule, one thread, no GPU: hit[r] (nrec
+ * entries) = the lowest pattern index occurring in record r, or 0xFFFFFFFF;
+ * seen[q] |= 1 (nq bytes, may be NULL) where pattern q occurs in some record.
+ * lens: the records' lengths; fails when they do not sum to seq_len. */
+int fqz5_seqs_scan_host(const fqz5_seq_table *, const uint8_t *seq, uint64_t seq_len,
+                        const uint32_t *lens, uint64_t nrec, uint32_t *hit, uint8_t *seen);
+
+/* d_seq[0..seq_len) (device) holds the bases of nrec records whose lengths
+ * are h_len (host).  The records that contain a pattern: their indices,
+ * ascending, into d_rec and each one's lowest pattern index into d_query
+ * (device, nrec entries each), *n_hit their number.  pairs != 0: a hit on
+ * record 2k or 2k + 1 selects both (a mate past nrec is ignored); the query
+ * index of one that did not match itself is 0xFFFFFFFF.  d_seen (device, nq
+ * bytes, may be NULL): byte q is set to 1 where pattern q occurs in some
+ * record, also where a lower pattern occurs in every such record; it is never
+ * cleared, so one buffer serves a whole file.  Fails when the lengths do not
+ * sum to seq_len or nrec >= 2^31. */
+int fqz5_seqs_match(const fqz5_seq_table *, const uint8_t *d_seq, uint64_t seq_len,
+                    const uint32_t *h_len, uint64_t nrec, int pairs,
+                    uint32_t *d_rec, uint32_t *d_query, uint64_t *n_hit, uint8_t *d_seen);
+
 #ifdef __cplusplus
 }
 #endif
