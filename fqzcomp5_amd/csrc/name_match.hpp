@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <vector>
 
 namespace fqz5 {
 
@@ -47,5 +48,13 @@ struct GpuCtx;
 // after synchronising g's stream; scratch comes from g's arena.
 uint32_t nm_compact(GpuCtx &g, const uint32_t *hit, uint32_t n, int pairs, uint32_t *d_rec,
                     uint32_t *d_query);
+
+// seq_match.hip: where each of a block's records ends in its base array (the
+// inclusive scan of the lengths: record r holds the positions below end[r]),
+// for the sequence matcher and the statistics (stats.hip);
+// throws GpuError("<who>: the record lengths do not sum to the bases") unless
+// the last end is seq_len.
+std::vector<uint64_t> record_ends(const uint32_t *lens, uint64_t nrec, uint64_t seq_len,
+                                  const char *who);
 
 }  // namespace fqz5

@@ -161,7 +161,9 @@ SmDev device_copy(fqz5_seq_table &T) {
     return SmDev{T.d_slots, T.d_q, T.d_qoff, T.mask, T.anchor, T.tag_bits};
 }
 
-// the records' inclusive ends; fails unless the last is seq_len
+}  // namespace
+
+// the records' inclusive ends; fails unless the last is seq_len (name_match.hpp)
 std::vector<uint64_t> record_ends(const uint32_t *lens, uint64_t nrec, uint64_t seq_len,
                                   const char *who) {
     std::vector<uint64_t> end(static_cast<size_t>(nrec));
@@ -172,7 +174,6 @@ std::vector<uint64_t> record_ends(const uint32_t *lens, uint64_t nrec, uint64_t 
     return end;
 }
 
-}  // namespace
 }  // namespace fqz5
 
 using namespace fqz5;

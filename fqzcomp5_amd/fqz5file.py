@@ -37,6 +37,10 @@ fqzcomp5 writes, produced and read by this library alone.
                                      the patterns (fqz5_seqs_match) -> names
                                      and quality decoded for the blocks with
                                      hits only -> fqz5_fastq_format_list
+    stats(src)                       read QC statistics in one pass: sequence
+                                     and quality sections decoded, histogrammed
+                                     on the device (fqz5_stats_add); no names,
+                                     no text, only the tables come back
 
 File layout (fqzcomp5.c:2563-2630, :2959-2969): "FQZ5\\1\\1\\0\\0", u64 index
 offset, the blocks, then "FQZ5IDX\\0", u32 nblocks and per block {u64 file
@@ -143,6 +147,23 @@ def _load():
         so.fqz5_seqs_match.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                        C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
                                        C.c_void_p]
+        so.fqz5_stats_new.restype = C.c_void_p
+        so.fqz5_stats_new.argtypes = [C.c_uint32, C.c_int]
+        so.fqz5_stats_free.restype = None
+        so.fqz5_stats_free.argtypes = [C.c_void_p]
+        so.fqz5_stats_words.restype = C.c_uint64
+        so.fqz5_stats_words.argtypes = [C.c_uint32, C.c_int]
+        so.fqz5_stats_tile.restype = C.c_uint32
+        so.fqz5_stats_tile.argtypes = []
+        so.fqz5_stats_add.restype = C.c_int
+        so.fqz5_stats_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                      C.c_uint64, C.c_void_p, C.c_void_p]
+        so.fqz5_stats_read.restype = C.c_int
+        so.fqz5_stats_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        so.fqz5_stats_host.restype = C.c_int
+        so.fqz5_stats_host.argtypes = [C.c_uint32, C.c_int, C.c_char_p, C.c_char_p, C.c_uint64,
+                                       C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
+                                       C.c_void_p]
         _bound = True
     return so
 
@@ -155,8 +176,9 @@ def _load():
 # match, decode, format, download, write; find_seqs / extract_seqs_file: the
 # same with seqs, the sequence sections decoded, in place of names, after
 # table, the patterns expanded and their table built, and before result, the
-# hits mapped back to the caller's patterns); the stages end with what the
-# library synchronises
+# hits mapped back to the caller's patterns; stats: index, read, upload,
+# decode, stats, the histogram kernels, and result, the tables' download);
+# the stages end with what the library synchronises
 _TRACE = {}
 
 
@@ -2538,4 +2560,243 @@ def extract_seqs_file(src: str, dst: str, patterns, revcomp: bool = False, plus_
     finally:
         rd.close()
     _trace_dump("extract_seqs")
+    return res
+
+
+# ---------------------------------------------------------------------------
+# File statistics
+#
+# "What is in this file?": read and base counts, the length distribution and
+# Nx, base composition and GC content, the quality distribution and quality
+# by cycle, without decoding a name, laying out text or downloading anything
+# but the final tables.  One pass over the file in windows, as the lookups
+# walk it: every block is read, checked against its index entry, parsed and
+# CRC-checked; one section decode per window holds the SEC_SEQ section of
+# every block and the SEC_QUAL section of every block that has one (FASTA
+# blocks have none; their records count in the length and base tables only);
+# fqz5_stats_add (stats.hip) then histograms each block's bases and qualities
+# into one device accumulator, which comes back once at the end.  The length
+# distribution is built here from the lengths the block headers give and kept
+# sparse.  One process.  Not built: several ranks, per-tile or flowcell
+# statistics from the names, k-mer or duplication levels, adapter content,
+# filtering records by these metrics.
+# ---------------------------------------------------------------------------
+STATS_CYCLES_MAX = 1 << 16
+
+
+def _stats_unpack(flat: np.ndarray, cycles: int, mates: int) -> dict:
+    """The tables of fqz5_stats_read / fqz5_stats_host (include/fqz5_fastq.h)
+    as arrays with a leading axis of `mates`."""
+    t = np.asarray(flat, np.uint64).reshape(mates, 873 + 262 * cycles)
+    cb = 873 + 6 * cycles
+    return {"records": t[:, 0].copy(), "bases": t[:, 1].copy(), "qual_records": t[:, 2].copy(),
+            "empty": t[:, 3].copy(), "base_counts": t[:, 4:260].copy(),
+            "qual_counts": t[:, 260:516].copy(), "read_qual": t[:, 516:772].copy(),
+            "read_gc": t[:, 772:873].copy(),
+            "cycle_base": t[:, 873:cb].reshape(mates, cycles, 6).copy(),
+            "cycle_qual": t[:, cb:].reshape(mates, cycles, 256).copy()}
+
+
+def _stats_host(seq: bytes, qual, lens, cycles: int, mates: int, out=None, per_record=False):
+    """fqz5_stats_host of one block added to `out` (a new zeroed table by
+    default): (the flat table, record_qsum, record_gc)."""
+    so = _load()
+    lens = np.ascontiguousarray(lens, np.uint32)
+    if out is None:
+        out = np.zeros(int(so.fqz5_stats_words(cycles, mates)), np.uint64)
+    qs = np.zeros(len(lens), np.uint64) if per_record else None
+    gc = np.zeros(len(lens), np.uint32) if per_record else None
+    _check(so.fqz5_stats_host(cycles, mates, bytes(seq), None if qual is None else bytes(qual),
+                              len(seq), lens.ctypes.data, len(lens), out.ctypes.data, len(out),
+                              qs.ctypes.data if per_record else None,
+                              gc.ctypes.data if per_record else None), "fqz5_stats_host")
+    return out, qs, gc
+
+
+class _StatsAcc:
+    """fqz5_stats, the device accumulator (freed on exit)."""
+
+    def __init__(self, cycles: int, mates: int):
+        self.so = _load()
+        self.cycles, self.mates = cycles, mates
+        self.p = self.so.fqz5_stats_new(cycles, mates)
+        if not self.p:
+            raise _lib.NativeError("fqz5_stats_new: " + _lib.last_error())
+
+    def add(self, d_seq: int, d_qual, seq_len: int, lens, d_qsum=None, d_gc=None) -> int:
+        """fqz5_stats_add's return code (callers raise)."""
+        lens = np.ascontiguousarray(lens, np.uint32)
+        return self.so.fqz5_stats_add(self.p, d_seq, d_qual, seq_len, lens.ctypes.data, len(lens),
+                                      d_qsum, d_gc)
+
+    def read(self) -> np.ndarray:
+        out = np.zeros(int(self.so.fqz5_stats_words(self.cycles, self.mates)), np.uint64)
+        _check(self.so.fqz5_stats_read(self.p, out.ctypes.data, len(out)), "fqz5_stats_read")
+        return out
+
+    def close(self) -> None:
+        if self.p:
+            self.so.fqz5_stats_free(self.p)
+            self.p = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def _merge_lengths(a, b):
+    """Two sparse length distributions (values ascending, counts) as one."""
+    v, inv = np.unique(np.concatenate([a[0], b[0]]), return_inverse=True)
+    c = np.zeros(len(v), np.uint64)
+    np.add.at(c, inv, np.concatenate([a[1], b[1]]))
+    return v, c
+
+
+class Stats:
+    """The result of stats(): every table has a leading axis of `mates` (1,
+    or 2 with pairs: record r of the file belongs to mate r & 1), counts are
+    np.uint64.
+
+    records, bases, qual_records (records of blocks that have qualities),
+    empty (records of length 0): [mates].
+    lengths: per mate (distinct record lengths ascending, their counts).
+    base_counts [mates, 256]: each sequence byte, case kept; qual_counts
+    [mates, 256]: each quality (the quality line's byte - 33).
+    cycles: C = min(the caller's cap, the longest record of the file);
+    cycle_base [mates, C, 6]: at position c the records longer than c by their
+    base there: A, C, G, T, N, other (case folded); cycle_qual [mates, C, 256]:
+    likewise by quality.
+    read_qual [mates, 256]: records with qualities and length L > 0 by
+    floor(sum of qualities / L); read_gc [mates, 101]: records of length L > 0
+    by floor(100 * G/C bases / L).
+    record_len (u32), record_gc (u32), record_qsum (u64, 0 without
+    qualities): per record in file order with per_record, else None."""
+
+    def __init__(self, mates: int, tables: dict, lengths, cycles: int, record_len=None,
+                 record_gc=None, record_qsum=None):
+        self.mates, self.cycles, self.lengths = mates, cycles, lengths
+        for k, v in tables.items():
+            setattr(self, k, v)
+        self.record_len, self.record_gc, self.record_qsum = record_len, record_gc, record_qsum
+
+    def nx(self, x: float, mate: int = 0) -> int:
+        """The Nx length: the largest v such that the records of length >= v
+        hold at least x % of the mate's bases (N50: nx(50)); 0 without bases."""
+        v, c = self.lengths[mate]
+        total = sum(int(a) * int(b) for a, b in zip(v, c))
+        cum = 0
+        for a, b in zip(v[::-1], c[::-1]):
+            cum += int(a) * int(b)
+            if total and cum * 100 >= x * total:
+                return int(a)
+        return 0
+
+
+def _stats(rd, cycles: int, mates: int, per_record: bool, device: str, window_bytes) -> Stats:
+    import torch
+    with _stage("index"):
+        index = read_index(rd)
+    wb = window_bytes or DEFAULT_WINDOW
+    groups, cur, tot = [], [], 0
+    for b, (s, t, _) in enumerate(index):
+        if cur and tot + t - s > wb:
+            groups.append(cur)
+            cur, tot = [], 0
+        cur.append(b)
+        tot += t - s
+    if cur:
+        groups.append(cur)
+    none = (np.zeros(0, np.uint32), np.zeros(0, np.uint64))
+    lengths = [none] * mates
+    rlen, rgc, rqs = [], [], []
+    with _StatsAcc(cycles, mates) as acc:
+        for grp in groups:
+            a, e = index[grp[0]][0], index[grp[-1]][1]
+            with _stage("read"):
+                hv = rd.read(a, e)
+                if len(hv) != e - a:
+                    raise _lib.NativeError("index disagrees with the file: a block past its end")
+            for b in grp:
+                _check_entry(index, b, hv, a)
+            with _stage("upload"):
+                buf = torch.from_numpy(np.ascontiguousarray(hv)).to(device)   # blocking
+            with _stage("decode"):
+                ranges = Blocks([(index[b][0] - a, index[b][1] - a) for b in grp], index.version)
+                views, lens, fasta = _parse_checked(hv, buf, ranges)
+                # per block its bases, then (unless FASTA) its qualities
+                at = np.concatenate([[0], np.cumsum([v.seq_ulen * (1 if fa else 2)
+                                                     for v, fa in zip(views, fasta)])])
+                out_d = torch.empty(int(at[-1]) + 1, dtype=torch.uint8, device=device)
+                base, secs = buf.data_ptr(), []
+                for j, (v, ln, fa) in enumerate(zip(views, lens, fasta)):
+                    rl = ln.ctypes.data_as(C.POINTER(C.c_uint32))
+                    d_seq = out_d.data_ptr() + int(at[j])
+                    secs.append(S.Section(base + ranges[j][0] + v.seq_off, d_seq, v.seq_size,
+                                          v.seq_ulen, 0, S.SEC_SEQ, rl, None, len(ln), None))
+                    if not fa:    # (the quality decoder reads the block's decoded bases)
+                        secs.append(S.Section(base + ranges[j][0] + v.qual_off, d_seq + v.seq_ulen,
+                                              v.qual_size, v.qual_ulen, 0, S.SEC_QUAL, rl, None,
+                                              len(ln), d_seq))
+                if any(r.status != 0 for r in S.decode(secs)):
+                    raise _lib.NativeError("section decoding failed: " + _lib.last_error())
+            with _stage("stats"):
+                nw = sum(len(ln) for ln in lens)
+                if per_record:
+                    qs_d = torch.empty(nw + 1, dtype=torch.int64, device=device)
+                    gc_d = torch.empty(nw + 1, dtype=torch.int32, device=device)
+                _lib.after_torch(device)
+                r0 = 0
+                for j, (v, ln, fa) in enumerate(zip(views, lens, fasta)):
+                    d_seq = out_d.data_ptr() + int(at[j])
+                    _check(acc.add(d_seq, None if fa else d_seq + v.seq_ulen, v.seq_ulen, ln,
+                                   qs_d.data_ptr() + 8 * r0 if per_record else None,
+                                   gc_d.data_ptr() + 4 * r0 if per_record else None),
+                           "fqz5_stats_add")
+                    r0 += len(ln)
+                for m in range(mates):
+                    for ln in lens:
+                        v, c = np.unique(ln[m::mates], return_counts=True)
+                        lengths[m] = _merge_lengths(lengths[m], (v, c.astype(np.uint64)))
+                if per_record:
+                    rlen.extend(lens)
+                    rqs.append(qs_d[:nw].cpu().numpy().view(np.uint64))
+                    rgc.append(gc_d[:nw].cpu().numpy().view(np.uint32))
+            del buf, hv, out_d
+        with _stage("result"):
+            flat = acc.read()
+    with _stage("result"):
+        longest = max((int(v[-1]) for v, _ in lengths if len(v)), default=0)
+        c = min(cycles, longest)
+        tab = _stats_unpack(flat, cycles, mates)
+        tab["cycle_base"] = tab["cycle_base"][:, :c].copy()
+        tab["cycle_qual"] = tab["cycle_qual"][:, :c].copy()
+        cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dt)
+        return Stats(mates, tab, lengths, c,
+                     *((cat(rlen, np.uint32), cat(rgc, np.uint32), cat(rqs, np.uint64))
+                       if per_record else ()))
+
+
+def stats(src, cycles: int = 1024, pairs: bool = False, per_record: bool = False,
+          device: str = "cuda", window_bytes: int | None = None) -> Stats:
+    """Read QC statistics of a .fqz5 (a path, the file's bytes, or a
+    positioned reader) as a Stats, histogrammed on the GPU (see above): one
+    pass in windows of at most `window_bytes` of compressed data; every block
+    is read once, checked against its index entry and CRC-checked, and its
+    sequence and quality sections decoded; no name section is decoded, no
+    text is formatted and only the tables come back.  cycles: the cap on the
+    per-cycle tables, 1..65536.  pairs: the records are interleaved pairs and
+    every table is kept per mate (a block with an odd record count is an
+    error).  per_record: also each record's length, G/C count and quality sum,
+    in file order.  One process."""
+    if not 1 <= cycles <= STATS_CYCLES_MAX:
+        raise ValueError(f"stats: cycles {cycles} not in 1..{STATS_CYCLES_MAX}")
+    rd, close = _reader(src)
+    try:
+        res = _stats(rd, cycles, 2 if pairs else 1, per_record, device, window_bytes)
+    finally:
+        if close:
+            rd.close()
+    _trace_dump("stats")
     return res

@@ -30,6 +30,11 @@
  *   fqz5_names_*        lookup by read name: a query table built on the host,
  *                       matched against a decoded name section on the device
  *                       (fqz5file.find_names / extract_names_file).
+ *   fqz5_seqs_*         lookup by sequence content: a pattern table built on
+ *                       the host, matched against a block's decoded bases.
+ *   fqz5_stats_*        read QC statistics: a block's decoded bases and
+ *                       qualities histogrammed into a device accumulator
+ *                       (fqz5file.stats).
  *
  * Offsets are bytes into the text.  Calls return 0 (fqz5_fastq_index: 1 for
  * FASTA text; fqz5_fastq_blocks: the block count) or -1 with
@@ -220,6 +225,64 @@ int fqz5_seqs_scan_host(const fqz5_seq_table *, const uint8_t *seq, uint64_t seq
 int fqz5_seqs_match(const fqz5_seq_table *, const uint8_t *d_seq, uint64_t seq_len,
                     const uint32_t *h_len, uint64_t nrec, int pairs,
                     uint32_t *d_rec, uint32_t *d_query, uint64_t *n_hit, uint8_t *d_seen);
+
+/* Read QC statistics (stats.hip; fqz5file.stats): counts over the decoded
+ * bases and qualities of a file's blocks, added block by block into one
+ * device accumulator.  mates is 1 or 2; with 2, record r of a block belongs
+ * to mate r & 1 and a block holds whole pairs.  A quality q is the quality
+ * line's byte - 33 (what the decoder leaves on the device).
+ *
+ * The tables are u64 words, one mate's after the other; a mate's
+ * W = 873 + 262 * cycles words are
+ *     [0] records  [1] bases  [2] qual_records (records of blocks that have
+ *     qualities)  [3] empty (records of length 0)
+ *     [4, 260)     base_counts[256]  count of each sequence byte, case kept
+ *     [260, 516)   qual_counts[256]  count of each q
+ *     [516, 772)   read_qual[256]    records of length L > 0 with qualities,
+ *                                    by floor(sum(q) / L)
+ *     [772, 873)   read_gc[101]      records of length L > 0, by
+ *                                    floor(100 * gc / L), gc its bytes in "GCgc"
+ *     [873, 873 + 6 * cycles)        cycle_base[cycles][6]: at position c, the
+ *                                    records longer than c by the class of
+ *                                    their byte there: A, C, G, T, N, other
+ *                                    (case folded)
+ *     [873 + 6 * cycles, W)          cycle_qual[cycles][256]: likewise by q
+ * Positions at or past `cycles` count in the whole-file tables only. */
+typedef struct fqz5_stats fqz5_stats;
+
+/* a zeroed accumulator on the calling thread's device; cycles 1..65536
+ * (NULL with fqz5_last_error() set otherwise) */
+fqz5_stats *fqz5_stats_new(uint32_t cycles, int mates);
+void fqz5_stats_free(fqz5_stats *);
+
+/* mates * W: the words fqz5_stats_read and fqz5_stats_host fill */
+uint64_t fqz5_stats_words(uint32_t cycles, int mates);
+
+/* bases per tile of the kernels */
+uint32_t fqz5_stats_tile(void);
+
+/* Add one block: d_seq[0..seq_len) and d_qual[0..seq_len) (device; d_qual
+ * NULL: a block without qualities, the quality tables and qual_records stay
+ * as they are) hold nrec records whose lengths are h_lens (host).  d_rec_qsum
+ * / d_rec_gc (device, nrec entries each, either may be NULL): per record the
+ * sum of its q (0 without qualities) and its number of G/C bytes, the values
+ * read_qual and read_gc are binned from.  The record ends are uploaded once
+ * per call.  Fails when the lengths do not sum to seq_len, on an odd nrec
+ * with two mates, or nrec >= 2^31, each before anything is added. */
+int fqz5_stats_add(fqz5_stats *, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t seq_len,
+                   const uint32_t *h_lens, uint64_t nrec, uint64_t *d_rec_qsum,
+                   uint32_t *d_rec_gc);
+
+/* the tables so far into h_out (host, cap words, at least fqz5_stats_words) */
+int fqz5_stats_read(const fqz5_stats *, uint64_t *h_out, uint64_t cap);
+
+/* Host restatement of the kernels' rule, one thread, no GPU: the block's
+ * counts are added to h_out (the same layout, cap words; zero it before the
+ * first block); rec_qsum / rec_gc (host, may be NULL) as above.  Fails as
+ * fqz5_stats_new and fqz5_stats_add do, before anything is added. */
+int fqz5_stats_host(uint32_t cycles, int mates, const uint8_t *seq, const uint8_t *qual,
+                    uint64_t seq_len, const uint32_t *lens, uint64_t nrec, uint64_t *h_out,
+                    uint64_t cap, uint64_t *rec_qsum, uint32_t *rec_gc);
 
 #ifdef __cplusplus
 }
