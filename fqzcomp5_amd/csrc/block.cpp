@@ -26,6 +26,7 @@
 #include "rans_codec.hpp"
 #include "fqz_codec.hpp"
 #include "seq_codec.hpp"
+#include "seq_cm.h"
 #include "lzp_codec.hpp"
 #include "names.hpp"
 #include "host_dec.hpp"
@@ -343,6 +344,8 @@ void fqz5_rans_variant_counts(uint64_t *dec, uint64_t *dec_hedged, uint64_t *enc
     rans_variant_counts(dec, dec_hedged, enc, ndec, nenc);
 }
 const char *fqz5_rans_variant_name(int dir, int i) { return rans_variant_name(dir, i); }
+
+int fqz5_seq_path_counts(uint64_t *out, int n) { return seq_path_counts(out, n); }
 
 void fqz5_trial_counts(uint64_t *out2) {
     out2[0] = g_fqz_tried.load();

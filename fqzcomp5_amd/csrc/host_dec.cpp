@@ -258,7 +258,7 @@ int fqz_decode(const uint8_t *in, size_t in_size, uint8_t *out, size_t out_cap, 
 // run lengths per class, literals for the rest, class switches
 int seq_decode(const uint8_t *in, uint32_t in_size, const uint32_t *lens, int nrec, int both, int ksz,
                uint8_t *out, uint32_t n) {
-    if (ksz < 1 || ksz > 16 || nrec <= 0) return -1;
+    if (ksz < 1 || ksz > 14 || nrec <= 0) return -1;   // as the GPU entries (SEQ_K_MAX)
     const uint32_t msize = 1u << (2 * ksz), mask = msize - 1;
     SeqScratch &S = t_seq;
     if (S.ctx.size() < size_t(msize) * 4) S.ctx.resize(size_t(msize) * 4);

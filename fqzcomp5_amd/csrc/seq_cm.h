@@ -58,4 +58,14 @@ hipError_t launch_seq_models_init(uint32_t *models, size_t nctx, hipStream_t s);
 // bases ahead (k_seq_dec_la); else the one-step decoder
 hipError_t launch_seq_dec(const SeqDecJob *d_jobs, int njobs, hipStream_t s, bool lookahead);
 
+// fqz5_seq_path_counts: decoder jobs per kernel (k_seq_dec_la, k_seq_dec),
+// launches of the per-event model pass ($FQZ5_SEQ_MODEL_EVENTS) and of
+// k_seq_model_runs per tile width (span / 256 = 1..16).  Host side only.
+enum : int {
+    SEQ_PATH_DEC_LA = 0, SEQ_PATH_DEC_ONE, SEQ_PATH_MODEL_EVENTS, SEQ_PATH_MODEL_SPAN,
+    SEQ_PATH_COUNT = SEQ_PATH_MODEL_SPAN + 16
+};
+void seq_path_add(int i, uint64_t n = 1);
+int seq_path_counts(uint64_t *out, int n);
+
 }  // namespace fqz5

@@ -19,6 +19,7 @@
 // Decoder.  Each symbol selects the next context, so a block is one chain
 // (k_seq_dec).
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 
 #include "fqz_model.hpp"
@@ -871,6 +872,13 @@ __global__ __launch_bounds__(64) void k_seq_dec_la(const SeqDecJob *Js) {
 // ---------------------------------------------------------------------------
 static dim3 grid_of(uint64_t n) { return dim3(unsigned((n + 255) / 256)); }
 
+static std::atomic<uint64_t> g_seq_path[SEQ_PATH_COUNT];
+void seq_path_add(int i, uint64_t n) { g_seq_path[i].fetch_add(n, std::memory_order_relaxed); }
+int seq_path_counts(uint64_t *out, int n) {
+    for (int i = 0; i < n && i < SEQ_PATH_COUNT; i++) out[i] = g_seq_path[i].load(std::memory_order_relaxed);
+    return SEQ_PATH_COUNT;
+}
+
 hipError_t launch_seq_heads(const SeqJob &j, hipStream_t s) {
     if (j.n) hipLaunchKernelGGL(k_seq_heads, grid_of(j.n), dim3(256), 0, s, j);
     return hipGetLastError();
@@ -891,6 +899,7 @@ hipError_t launch_seq_model(const SeqJob &j, hipStream_t s) {
     if (!j.nkeys) return hipGetLastError();
     static const bool per_event = std::getenv("FQZ5_SEQ_MODEL_EVENTS") != nullptr;
     if (per_event) {
+        seq_path_add(SEQ_PATH_MODEL_EVENTS);
         hipLaunchKernelGGL(k_seq_model, grid_of(j.nkeys), dim3(256), 0, s, j);
         return hipGetLastError();
     }
@@ -898,6 +907,7 @@ hipError_t launch_seq_model(const SeqJob &j, hipStream_t s) {
     const uint64_t nctx = std::min<uint64_t>(uint64_t(j.mask) + 1, j.nkeys);
     const uint64_t run = std::min<uint64_t>((j.nkeys + nctx - 1) / nctx, SEQ_SPAN_MAX / 256);
     const uint32_t span = uint32_t(256 * std::max<uint64_t>(run, 1));
+    seq_path_add(SEQ_PATH_MODEL_SPAN + int(span / 256) - 1);
     hipLaunchKernelGGL(k_seq_model_runs, dim3(unsigned((j.nkeys + span - 1) / span)), dim3(256), 0, s,
                        j, span);
     return hipGetLastError();

@@ -238,6 +238,8 @@ void seq_decode_batch(GpuCtx &g, std::vector<SeqDecReq> &reqs) {
     // k >= 3: the lookahead decoder; the rest (k = 1, 2) the one-step one
     std::vector<SeqDecJob> la, one;
     for (const SeqDecJob &J : js) (J.k >= 3 ? la : one).push_back(J);
+    seq_path_add(SEQ_PATH_DEC_LA, la.size());
+    seq_path_add(SEQ_PATH_DEC_ONE, one.size());
     if (!la.empty()) FQZ5_HIP(launch_seq_dec(g.upload(la), int(la.size()), g.stream, true));
     if (!one.empty()) FQZ5_HIP(launch_seq_dec(g.upload(one), int(one.size()), g.stream, false));
     ev.stop(g.stream);
@@ -330,6 +332,58 @@ char *fqz5_seq_decode(unsigned char *in, unsigned int in_size, unsigned int *len
         fqz5_set_error(e.what());
         try { if (gp) gp->reset(); } catch (...) {}
         return nullptr;
+    }
+}
+
+int fqz5_seq_decode_many(int n, const unsigned char *const *in, const unsigned int *in_size,
+                         const unsigned int *const *len, const int *nrecords,
+                         const int *both_strands, const int *ctx_size, const unsigned int *out_size,
+                         int in_offset, unsigned char *const *out, int *status) {
+    GpuCtx *gp = nullptr;
+    try {
+        if (n < 0 || in_offset < 0 || in_offset > 15 ||
+            (n && (!in || !in_size || !len || !nrecords || !both_strands || !ctx_size || !out_size ||
+                   !out || !status)))
+            throw GpuError("fqz5_seq_decode_many: bad arguments");
+        // the streams back to back from in_offset on, then 16 bytes that are
+        // no stream's (a chunk with a stream's end in it reads the rest as 0)
+        std::vector<uint8_t> pack(size_t(in_offset), uint8_t(0xA5));
+        std::vector<size_t> at(size_t(n), 0);
+        for (int i = 0; i < n; i++) {
+            if ((!in[i] && in_size[i]) || !len[i] || nrecords[i] < 1 || (!out[i] && out_size[i]))
+                throw GpuError("fqz5_seq_decode_many: bad arguments");
+            at[size_t(i)] = pack.size();
+            pack.insert(pack.end(), in[i], in[i] + in_size[i]);
+        }
+        pack.insert(pack.end(), 16, uint8_t(0xA5));
+        GpuCtx &g = gpu();
+        gp = &g;
+        const uint8_t *d_pack = g.upload(pack);
+        std::vector<SeqDecReq> rq(size_t(n), SeqDecReq{});
+        for (int i = 0; i < n; i++) {
+            SeqDecReq &R = rq[size_t(i)];
+            R.d_in = d_pack + at[size_t(i)];
+            R.in_size = in_size[i];
+            R.lens = len[i];
+            R.nrec = nrecords[i];
+            R.both = both_strands[i];
+            R.k = ctx_size[i];
+            R.n = out_size[i];
+            R.d_out = g.arena.alloc_n<uint8_t>(out_size[i] ? out_size[i] : 1);
+            g.memset0(R.d_out, out_size[i]);
+        }
+        seq_decode_batch(g, rq);
+        for (int i = 0; i < n; i++) {
+            g.download(out[i], rq[size_t(i)].d_out, out_size[i]);
+            status[i] = rq[size_t(i)].ok ? 0 : -1;
+        }
+        g.sync();
+        g.reset();
+        return 0;
+    } catch (const std::exception &e) {
+        fqz5_set_error(e.what());
+        try { if (gp) gp->reset(); } catch (...) {}
+        return -1;
     }
 }
 

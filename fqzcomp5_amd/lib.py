@@ -553,6 +553,49 @@ def seq_decode(comp: bytes, lens, both: int, k: int, out_size: int, host: bool =
     return out
 
 
+SEQ_PATH_NAMES = (["dec_lookahead", "dec_one_step", "model_events"] +
+                  ["model_span_%d" % (256 * (i + 1)) for i in range(16)])
+
+
+def seq_path_counts() -> dict[str, int]:
+    """fqz5_seq_path_counts: sequence-model decoder jobs per kernel and
+    model-pass launches per tile width (or in the per-event form)."""
+    so = load()
+    so.fqz5_seq_path_counts.restype = C.c_int
+    so.fqz5_seq_path_counts.argtypes = [C.POINTER(C.c_uint64), C.c_int]
+    out = (C.c_uint64 * len(SEQ_PATH_NAMES))()
+    if so.fqz5_seq_path_counts(out, len(SEQ_PATH_NAMES)) != len(SEQ_PATH_NAMES):
+        raise NativeError("fqz5_seq_path_counts: the library counts other paths")
+    return {k: int(v) for k, v in zip(SEQ_PATH_NAMES, out)}
+
+
+def seq_decode_many(streams, in_offset: int = 0) -> list[tuple[int, bytes]]:
+    """fqz5_seq_decode_many: streams of (comp, lens, both, k, out_size), packed
+    back to back on the device from in_offset (0..15) past a 16-byte boundary
+    and decoded in one batch; (status, bytes) per stream."""
+    so = load()
+    n = len(streams)
+    PU, PB = C.POINTER(C.c_uint32), C.POINTER(C.c_ubyte)
+    so.fqz5_seq_decode_many.restype = C.c_int
+    so.fqz5_seq_decode_many.argtypes = [C.c_int, C.POINTER(C.c_char_p), PU, C.POINTER(PU),
+                                        C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                        PU, C.c_int, C.POINTER(PB), C.POINTER(C.c_int)]
+    comps = [bytes(s[0]) for s in streams]
+    lens = [_seq_lens(s[1]) for s in streams]
+    outs = [(C.c_ubyte * max(int(s[4]), 1))() for s in streams]
+    ints = lambda v: (C.c_int * n)(*v)
+    status = ints([1] * n)
+    rc = so.fqz5_seq_decode_many(
+        n, (C.c_char_p * n)(*comps), (C.c_uint32 * n)(*[len(c) for c in comps]),
+        (PU * n)(*[C.cast(la, PU) for la, _ in lens]), ints([nr for _, nr in lens]),
+        ints([int(s[2]) for s in streams]), ints([int(s[3]) for s in streams]),
+        (C.c_uint32 * n)(*[int(s[4]) for s in streams]), in_offset,
+        (PB * n)(*[C.cast(o, PB) for o in outs]), status)
+    if rc != 0:
+        raise NativeError("fqz5_seq_decode_many failed: " + last_error())
+    return [(int(status[i]), bytes(outs[i])[:int(streams[i][4])]) for i in range(n)]
+
+
 def lzp(data: bytes) -> bytes:
     """fqz5_lzp (lzp16e.c:113 lzp) on the GPU."""
     so = load()

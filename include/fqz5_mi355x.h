@@ -135,7 +135,8 @@ char *fqz5_seq_encode(unsigned char *in, unsigned int in_size, unsigned int *len
                       unsigned int *out_size);
 
 /* Replaces decode_seq (fqzcomp5.c:1272): out_size bytes from a stream of
- * fqz5_seq_encode / encode_seq.  NULL on a damaged stream. */
+ * fqz5_seq_encode / encode_seq.  NULL on a damaged stream or a ctx_size
+ * outside 1..14 (fqz5_seq_decode_host alike). */
 char *fqz5_seq_decode(unsigned char *in, unsigned int in_size, unsigned int *len,
                       int nrecords, int both_strands, int ctx_size,
                       unsigned int out_size);
@@ -412,6 +413,28 @@ void fqz5_fqz_dec_counts(uint64_t *out2);
  * serial encoder and out[16] by the parallel one.  Fills min(n, 17)
  * entries and returns 17. */
 int fqz5_fqz_path_counts(uint64_t *out, int n);
+/* Sequence context model work since the library was loaded, by the code
+ * that took it: out[0] decoder jobs given to the look-ahead decoder
+ * (k_seq_dec_la, ctx_size 3..14), out[1] to the one-step decoder (k_seq_dec,
+ * ctx_size 1 and 2), out[2] launches of the per-event model pass
+ * ($FQZ5_SEQ_MODEL_EVENTS), out[3 + i] launches of the model pass over tiles
+ * of 256 * (i + 1) sorted events, i = 0..15.  Fills min(n, 19) entries and
+ * returns 19. */
+int fqz5_seq_path_counts(uint64_t *out, int n);
+
+/* fqz5_seq_decode for n streams in one launch per decoder kernel.  The
+ * streams are packed back to back into one device buffer that starts
+ * in_offset (0..15) bytes past a 16-byte boundary, so that a stream starts
+ * at any residue and ends against its neighbour's bytes.  Stream i has the
+ * arguments of fqz5_seq_decode at index i and its out_size[i] bytes go to
+ * out[i] (the caller's); status[i] is 0, or -1 for a damaged stream or a
+ * refused argument (ctx_size outside 1..14, records that run out).
+ * Returns 0, or -1 on a device error or a bad argument of the call itself. */
+int fqz5_seq_decode_many(int n, const unsigned char *const *in, const unsigned int *in_size,
+                         const unsigned int *const *len, const int *nrecords,
+                         const int *both_strands, const int *ctx_size,
+                         const unsigned int *out_size, int in_offset,
+                         unsigned char *const *out, int *status);
 
 /* Device check of the fqz decoder's division: floor(n / t) computed as
  * (u32)fma(n, recip(t), 2^-19) for every t < 2^16 and ~2000 n each.
