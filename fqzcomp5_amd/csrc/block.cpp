@@ -5,11 +5,13 @@
 // The reference encodes one block at a time per worker thread, trying every
 // method of the section's mask while the codec trial is running
 // (metrics_method / compress_with_methods, fqzcomp5.c:1899-2144).  Here a
-// whole run of blocks is handed over at once: every candidate method of
-// every block is compressed speculatively in ONE GPU batch (the chains run
-// side by side, so the extra candidates cost little wall time), then the
-// trial state machine is replayed on the host in block order, which gives
-// exactly the choices of a single-threaded (-t1) reference run.
+// whole run of blocks is handed over at once: the candidates of every block
+// are compressed in one try session (every method of the trial blocks; for
+// the others every rANS method, or with a staged try only the trial's pick,
+// predicted from the trial blocks' sizes: the long chains run on host cores,
+// one core each, so a candidate nobody reads is not free), then the trial
+// state machine is replayed on the host in block order, which gives exactly
+// the choices of a single-threaded (-t1) reference run.
 #include <atomic>
 #include <cstdio>
 #include <algorithm>
@@ -84,6 +86,21 @@ int method_order(int m, uint32_t fixed_len) {
     return int((fixed_len << 8) + 9);   // RANSXN1, incl. the >=256 aliasing
 }
 
+// The trial's pick among the methods of `among` (fqzcomp5.c:1913-1924): the
+// smallest (csize + 1) / usize, the first one on a tie; 0 if none was tried.
+int pick_method(const fqz5_section_stats &s, uint32_t among) {
+    int best_m = 0;
+    double best = 1e30;
+    for (int m = 0; m < FQZ5_M_LAST; m++) {
+        if (!(among & (1u << m))) continue;
+        if (s.usize[m] && best > (s.csize[m] + 1.0) / s.usize[m]) {
+            best = (s.csize[m] + 1.0) / s.usize[m];
+            best_m = m;
+        }
+    }
+    return best_m;
+}
+
 // metrics_method (fqzcomp5.c:1899-1946)
 uint32_t metrics_method(fqz5_trial_state &st, int sec, uint32_t avail) {
     fqz5_section_stats &s = st.sec[sec];
@@ -96,20 +113,107 @@ uint32_t metrics_method(fqz5_trial_state &st, int sec, uint32_t avail) {
     }
     if (s.trial > 0) return avail;
     if (s.trial > -99999) {
-        int best_m = 0;
-        double best = 1e30;
-        for (int m = 0; m < FQZ5_M_LAST; m++) {
-            if (s.usize[m] && best > (s.csize[m] + 1.0) / s.usize[m]) {
-                best = (s.csize[m] + 1.0) / s.usize[m];
-                best_m = m;
-            }
-        }
-        s.method_used = best_m;
+        s.method_used = pick_method(s, ~0u);
         s.trial = -99999;
-        return 1u << best_m;
+        return 1u << s.method_used;
     }
     s.review--;
     return 1u << s.method_used;
+}
+
+// metrics_method's counters without the sizes: what the next section of a
+// kind does.  Which sections try every method (trial and re-trial blocks)
+// does not depend on the outcomes.
+enum TrialStep { STEP_TRIAL, STEP_DECIDE, STEP_KEEP };
+TrialStep trial_step(fqz5_section_stats &ss, bool *fresh = nullptr) {
+    if (ss.review <= 0) {
+        ss.review = FQZ5_METRICS_REVIEW;
+        ss.trial = FQZ5_METRICS_TRIAL;
+        if (fresh) *fresh = true;
+    }
+    if (ss.trial > 0) {
+        ss.trial--;
+        return STEP_TRIAL;
+    }
+    if (ss.trial > -99999) {
+        ss.trial = -99999;
+        return STEP_DECIDE;
+    }
+    ss.review--;
+    return STEP_KEEP;
+}
+
+// One decision of a staged try (fqz5_sections_try_staged): a trial window of
+// a kind whose remaining sections lie in the call, and the sections after it
+// that take its pick.
+struct Decision {
+    int kind = 0;
+    bool fresh = false;            // the window began in the call: its sums start at zero
+    std::vector<int> rows;         // the window's sections in the call
+    std::vector<int> follow;       // the sections coded with its pick
+};
+
+// The role of every section of a call (file order) from the trial state
+// before its first section; see fqz5_staged_plan.
+void staged_walk(const int32_t *sec_ids, int nsec, const uint32_t *avail,
+                 const fqz5_trial_state *st, int32_t *roles, uint32_t *masks, int32_t *window,
+                 std::vector<Decision> *decs) {
+    fqz5_trial_state s = *st;
+    int cur[FQZ5_SEC_LAST], nwin[FQZ5_SEC_LAST], settled[FQZ5_SEC_LAST];
+    bool open[FQZ5_SEC_LAST];      // the kind's last window still takes trial sections
+    for (int k = 0; k < FQZ5_SEC_LAST; k++) {
+        cur[k] = -1;               // index in *decs of the decision that governs, -1: the state
+        nwin[k] = 0;
+        settled[k] = s.sec[k].method_used;
+        open[k] = false;
+    }
+    std::vector<Decision> local;
+    std::vector<Decision> &D = decs ? *decs : local;
+    for (int i = 0; i < nsec; i++) {
+        const int k = sec_ids[i];
+        fqz5_section_stats &ss = s.sec[k];
+        const bool staged = k == FQZ5_SEC_SEQ || k == FQZ5_SEC_QUAL;
+        bool fresh = false;
+        const TrialStep step = trial_step(ss, &fresh);
+        window[i] = -1;
+        if (step == STEP_TRIAL) {
+            roles[i] = staged ? FQZ5_ROLE_TRIAL : FQZ5_ROLE_OTHER;
+            masks[i] = avail[k];
+            if (!staged) continue;
+            if (!open[k]) {
+                Decision d;
+                d.kind = k;
+                d.fresh = fresh;
+                cur[k] = int(D.size());
+                D.push_back(d);
+                open[k] = true;
+                nwin[k]++;
+            }
+            D[size_t(cur[k])].rows.push_back(i);
+            window[i] = nwin[k] - 1;
+            continue;
+        }
+        if (!staged) {
+            roles[i] = FQZ5_ROLE_OTHER;
+            masks[i] = 0;
+            continue;
+        }
+        if (step == STEP_DECIDE && !open[k]) {
+            // the window ended before the call: its sums are in the state
+            settled[k] = pick_method(st->sec[k], ~0u);
+            cur[k] = -1;
+        }
+        open[k] = false;
+        if (cur[k] >= 0) {
+            roles[i] = FQZ5_ROLE_FOLLOW;
+            masks[i] = 0;
+            window[i] = nwin[k] - 1;
+            D[size_t(cur[k])].follow.push_back(i);
+        } else {
+            roles[i] = FQZ5_ROLE_SETTLED;
+            masks[i] = 1u << settled[k];
+        }
+    }
 }
 
 }  // namespace
@@ -133,6 +237,7 @@ struct TrySession {
     std::vector<std::vector<int>> name_of;
     bool open = false;
     bool aux = false;                             // candidates live in the helper contexts
+    std::vector<int> predicted;                   // staged try: a follow section's provisional method (else -1)
 };
 
 // fqz_compress(4, slice, in, size, &len, m - FQZ0, NULL) for a section
@@ -218,6 +323,20 @@ std::atomic<int> g_prune{0};
 // and codes the winners at commit (encode_run_bounded).
 std::atomic<int> g_bounds{0};
 std::atomic<uint64_t> g_fqz_tried{0}, g_fqz_pruned{0};
+// Staged tries (fqz5_set_staged_try, $FQZ5_STAGED_TRY; -1 = not read yet)
+std::atomic<int> g_staged{-1};
+std::atomic<uint64_t> g_staged_n[4];               // fqz5_staged_counts
+std::atomic<uint64_t> g_staged_dec[FQZ5_SEC_LAST]; // fqz5_staged_decisions
+bool staged_on() {
+    int v = g_staged.load();
+    if (v < 0) {
+        const char *e = std::getenv("FQZ5_STAGED_TRY");
+        v = !(e && e[0] == '0');
+        int want = -1;
+        if (!g_staged.compare_exchange_strong(want, v)) v = want;
+    }
+    return v != 0;
+}
 std::atomic<uint64_t> g_chains_host{0}, g_chains_gpu{0};   // fqz5_decode_chain_counts
 
 // Which requests of one family of work candidates (fqz methods FQZ0..FQZ4 on
@@ -354,33 +473,48 @@ void fqz5_trial_counts(uint64_t *out2) {
 
 void fqz5_trial_schedule(const int32_t *sec_ids, int nsec, const uint32_t *avail,
                          const fqz5_trial_state *st, uint32_t *masks_out) {
-    // metrics_method's counters without the sizes: which sections try every
-    // method (trial and re-trial blocks) does not depend on the outcomes
     fqz5_trial_state s = *st;
-    for (int i = 0; i < nsec; i++) {
-        fqz5_section_stats &ss = s.sec[sec_ids[i]];
-        if (ss.review <= 0) {
-            ss.review = FQZ5_METRICS_REVIEW;
-            ss.trial = FQZ5_METRICS_TRIAL;
-        }
-        masks_out[i] = 0;
-        if (ss.trial > 0) {
-            masks_out[i] = avail[sec_ids[i]];
-            ss.trial--;
-        } else if (ss.trial > -99999) {
-            ss.trial = -99999;
-        } else {
-            ss.review--;
-        }
-    }
+    for (int i = 0; i < nsec; i++)
+        masks_out[i] = trial_step(s.sec[sec_ids[i]]) == STEP_TRIAL ? avail[sec_ids[i]] : 0;
+}
+
+void fqz5_staged_plan(const int32_t *sec_ids, int nsec, const uint32_t *avail,
+                      const fqz5_trial_state *st, int32_t *roles_out, uint32_t *masks_out,
+                      int32_t *window_out) {
+    staged_walk(sec_ids, nsec, avail, st, roles_out, masks_out, window_out, nullptr);
+}
+
+int fqz5_set_staged_try(int on) {
+    const int prev = staged_on();
+    g_staged.store(on ? 1 : 0);
+    return prev;
+}
+
+void fqz5_staged_counts(uint64_t out[4]) {
+    for (int k = 0; k < 4; k++) out[k] = g_staged_n[k].load();
+}
+
+void fqz5_staged_decisions(uint64_t out[FQZ5_SEC_LAST]) {
+    for (int k = 0; k < FQZ5_SEC_LAST; k++) out[k] = g_staged_dec[k].load();
 }
 
 using host::now_ms;
 using host::now_ns;
 using host::step_trace;
 
-int fqz5_sections_try(const fqz5_section *secs, int nsec, const uint32_t *masks,
-                      uint32_t *sizes) {
+}  // extern "C"
+
+// fqz5_sections_try, and with `avail` and `st` (and staged tries on)
+// fqz5_sections_try_staged: the sequence and quality sections outside a trial
+// window code one method, the trial's pick.  A section whose pick is in the
+// state (settled) codes it beside the trial sections; a section whose trial
+// window lies in this call (follow) waits until the window's rANS candidates
+// have sizes, and is then coded with the pick over those sizes, while the
+// other helpers are still at work.  The pick is provisional: the replay
+// decides, and the commit codes late whatever the session lacks.
+static int sections_try_impl(const fqz5_section *secs, int nsec, const uint32_t *masks_in,
+                             uint32_t *sizes, const uint32_t *avail,
+                             const fqz5_trial_state *st) {
     const double t0 = step_trace() ? now_ms() : 0;
     try {
         GpuCtx &g = gpu();
@@ -389,6 +523,28 @@ int fqz5_sections_try(const fqz5_section *secs, int nsec, const uint32_t *masks,
             gpu_aux_reset_all();
         }
         t_sess = TrySession();
+        t_sess.predicted.assign(size_t(std::max(nsec, 0)), -1);
+        // the first stage's masks: a settled section keeps its one method, a
+        // follow section none
+        std::vector<uint32_t> stage1(masks_in, masks_in + std::max(nsec, 0));
+        std::vector<Decision> decs;
+        const bool staged = avail && st && staged_on() && nsec > 0;
+        if (staged) {
+            std::vector<int32_t> ids(nsec), roles(nsec), win(nsec);
+            std::vector<uint32_t> pm(nsec);
+            for (int i = 0; i < nsec; i++) ids[i] = secs[i].sec;
+            staged_walk(ids.data(), nsec, avail, st, roles.data(), pm.data(), win.data(), &decs);
+            uint64_t skipped = 0;
+            for (int i = 0; i < nsec; i++) {
+                if (roles[i] == FQZ5_ROLE_SETTLED) stage1[i] &= pm[i];
+                if (roles[i] == FQZ5_ROLE_FOLLOW) stage1[i] = 0;
+                uint32_t gone = masks_in[i] & ~stage1[i];
+                if (!secs[i].fixed_len) gone &= ~(1u << RANSXN1);
+                skipped += uint64_t(__builtin_popcount(gone));
+            }
+            g_staged_n[3] += skipped;        // (a follow section's coded pick comes off below)
+        }
+        const uint32_t *masks = stage1.data();
         for (int i = 0; i < nsec; i++) {
             if (masks[i] & ~(RANS_MASK | FQZ_MASK | SEQ_MASK | NAME_MASK | (1u << LZP3)))
                 throw GpuError("fqz5_sections_try: method mask has SEQ_CUSTOM (not in this build)");
@@ -465,6 +621,93 @@ int fqz5_sections_try(const fqz5_section *secs, int nsec, const uint32_t *masks,
                 reqs.push_back(std::move(sreq[k]));
             }
             sreq.clear();
+        };
+        if (staged)
+            g_staged_n[0] += reqs.size() + sreq.size() + lzp_sec.size() + fq.size() + sq.size();
+        // The second stage: each decision's pick over the sizes its window's
+        // rANS candidates have now (the first smallest (csize + 1) / usize,
+        // as metrics_method picks), and the follow sections coded with it; the
+        // plain chains on `plain_ctx` beside the others when there is one.
+        auto stage2 = [&](GpuCtx *plain_ctx) {
+            std::vector<CompressReq> s2;
+            std::vector<int> s2_sec, s2_m;
+            for (const Decision &d : decs) {
+                fqz5_section_stats s = st->sec[d.kind];
+                if (d.fresh) {
+                    std::memset(s.usize, 0, sizeof s.usize);
+                    std::memset(s.csize, 0, sizeof s.csize);
+                }
+                if (d.follow.empty()) continue;     // nothing in the call takes its pick
+                for (int i : d.rows)
+                    for (int m = 1; m < FQZ5_M_LAST; m++) {
+                        if (!(masks_in[i] & RANS_MASK & (1u << m))) continue;
+                        const int ri = t_sess.req_of[size_t(i)][m];
+                        s.usize[m] += secs[i].in_size;
+                        s.csize[m] += ri < 0 ? UINT32_MAX
+                                      : reqs[size_t(ri)].ok ? layout_size(reqs[size_t(ri)].out) : 0;
+                    }
+                const int w = pick_method(s, RANS_MASK);
+                g_staged_dec[d.kind]++;
+                if (step_trace())
+                    std::fprintf(stderr, "sections_try: staged: kind %d decided at %.1f ms: method %d "
+                                 "for %zu sections\n", d.kind, now_ms() - t0, w, d.follow.size());
+                if (!w) continue;
+                for (int i : d.follow) {
+                    const fqz5_section &S = secs[i];
+                    if (!(masks_in[i] & (1u << w)) || (w == RANSXN1 && !S.fixed_len)) continue;
+                    CompressReq r;
+                    r.d_in = S.in;
+                    r.n = S.in_size;
+                    r.order = method_order(w, S.fixed_len);
+                    r.cap = compress_bound(r.n, r.order);
+                    s2.push_back(std::move(r));
+                    s2_sec.push_back(i);
+                    s2_m.push_back(w);
+                }
+            }
+            if (s2.empty()) return;
+            std::vector<CompressReq> pl, rest;
+            std::vector<char> is_pl(s2.size(), 0);
+            for (size_t k = 0; k < s2.size(); k++)
+                is_pl[k] = plain_ctx && (s2[k].order & ~1) == 0 && s2[k].n >= (1u << 20);
+            for (size_t k = 0; k < s2.size(); k++) (is_pl[k] ? pl : rest).push_back(std::move(s2[k]));
+            if (pl.empty() || rest.empty()) {
+                compress_batch(g, pl.empty() ? rest : pl);
+            } else {
+                std::exception_ptr e2;
+                plain_ctx->prof.on = g.prof.on;
+                std::thread t2([&] {
+                    try {
+                        FQZ5_HIP(hipSetDevice(plain_ctx->device));
+                        compress_batch(*plain_ctx, pl);
+                    } catch (...) {
+                        e2 = std::current_exception();
+                    }
+                });
+                try {
+                    compress_batch(g, rest);
+                } catch (...) {
+                    t2.join();
+                    throw;
+                }
+                t2.join();
+                if (e2) std::rethrow_exception(e2);
+                g.prof.enc_ms += plain_ctx->prof.enc_ms;
+                g.prof.enc_launches += plain_ctx->prof.enc_launches;
+                g.prof.enc_bytes += plain_ctx->prof.enc_bytes;
+                plain_ctx->prof = KernelProfile();
+            }
+            size_t qp = 0, qr = 0;
+            for (size_t k = 0; k < s2_sec.size(); k++) {
+                t_sess.req_of[size_t(s2_sec[k])][s2_m[k]] = int(reqs.size());
+                t_sess.predicted[size_t(s2_sec[k])] = s2_m[k];
+                reqs.push_back(std::move(is_pl[k] ? pl[qp++] : rest[qr++]));
+            }
+            g_staged_n[1] += s2_sec.size();
+            g_staged_n[3] -= s2_sec.size();
+            if (step_trace())
+                std::fprintf(stderr, "sections_try: staged: stage 2 (%zu sections) done at %.1f ms\n",
+                             s2_sec.size(), now_ms() - t0);
         };
         if ((!fq.empty() || !sq.empty() || !lzp_sec.empty() || !sreq.empty() || !name_sec.empty()) &&
             !no_aux) {
@@ -560,34 +803,32 @@ int fqz5_sections_try(const fqz5_section *secs, int nsec, const uint32_t *masks,
                 tc = step_trace() ? now_ms() : 0;
                 tp.join();
                 tpl = step_trace() ? now_ms() : 0;
+                // the three rANS batches first (the stripes' too): their sizes
+                // decide the second stage, which runs beside the other helpers
+                ts.join();
+                if (perr) std::rethrow_exception(perr);
+                if (serr) std::rethrow_exception(serr);
+                for (size_t q = 0; q < plain_at.size(); q++) reqs[plain_at[q]] = std::move(plain[q]);
+                g.prof.enc_ms += gp.prof.enc_ms;
+                g.prof.enc_launches += gp.prof.enc_launches;
+                g.prof.enc_bytes += gp.prof.enc_bytes;
+                gp.prof = KernelProfile();
+                if (step_trace() && !plain_at.empty())
+                    std::fprintf(stderr, "sections_try: %zu plain rANS candidates on a helper, "
+                                 "done %.1f ms after the others\n", plain_at.size(), tpl - tc);
+                join_stripes();
+                if (staged) stage2(&gp);
+                tc = step_trace() ? now_ms() : 0;
             } catch (...) {
                 if (tp.joinable()) tp.join();
+                if (ts.joinable()) ts.join();
                 for (auto &t : th) t.join();
-                ts.join();
                 tn.join();
                 throw;
             }
-            if (perr) {
-                for (auto &t : th) t.join();
-                ts.join();
-                tn.join();
-                std::rethrow_exception(perr);
-            }
-            for (size_t q = 0; q < plain_at.size(); q++) reqs[plain_at[q]] = std::move(plain[q]);
-            g.prof.enc_ms += gp.prof.enc_ms;
-            g.prof.enc_launches += gp.prof.enc_launches;
-            g.prof.enc_bytes += gp.prof.enc_bytes;
-            gp.prof = KernelProfile();
-            if (step_trace() && !plain_at.empty())
-                std::fprintf(stderr, "sections_try: %zu plain rANS candidates on a helper, "
-                             "done %.1f ms after the others\n", plain_at.size(), tpl - tc);
-            tc = std::max(tc, tpl);
             for (auto &t : th) t.join();
-            ts.join();
             tn.join();
-            if (serr) std::rethrow_exception(serr);
             if (nerr) std::rethrow_exception(nerr);
-            join_stripes();
             if (step_trace())
                 std::fprintf(stderr, "sections_try: rANS candidates %.1f ms, helpers waited "
                              "%.1f ms more\n", tc - t0, now_ms() - tc);
@@ -637,6 +878,7 @@ int fqz5_sections_try(const fqz5_section *secs, int nsec, const uint32_t *masks,
             join_stripes();
             add_lzp3(g, secs, lzp_sec, reqs, t_sess.req_of);
             compress_batch(g, reqs);
+            if (staged) stage2(nullptr);
             encode_name_jobs(g, secs, name_sec, name_meth, t_sess.names);
             if (!fq.empty()) fqz_encode_batch(g, fq);
             if (!sq.empty()) seq_encode_batch(g, sq);
@@ -707,6 +949,19 @@ int fqz5_sections_try(const fqz5_section *secs, int nsec, const uint32_t *masks,
     }
 }
 
+extern "C" {
+
+int fqz5_sections_try(const fqz5_section *secs, int nsec, const uint32_t *masks,
+                      uint32_t *sizes) {
+    return sections_try_impl(secs, nsec, masks, sizes, nullptr, nullptr);
+}
+
+int fqz5_sections_try_staged(const fqz5_section *secs, int nsec, const uint32_t *masks,
+                             uint32_t *sizes, const uint32_t *avail,
+                             const fqz5_trial_state *st) {
+    return sections_try_impl(secs, nsec, masks, sizes, avail, st);
+}
+
 void fqz5_trial_replay(const int32_t *sec_ids, const uint32_t *in_sizes,
                        const uint32_t *sizes, int nsec, const uint32_t *avail,
                        fqz5_trial_state *st, int32_t *methods_out,
@@ -766,6 +1021,10 @@ int fqz5_sections_commit(const fqz5_section *secs, int nsec, const int32_t *meth
             const int q = t_sess.seq_of[i][m];
             return q >= 0 && !(size_t(q) < t_sess.seq_skip.size() && t_sess.seq_skip[size_t(q)]);
         };
+        for (int i = 0; i < nsec; i++)                // a staged try's picks the replay overturned
+            if (size_t(i) < t_sess.predicted.size() && t_sess.predicted[size_t(i)] >= 0 &&
+                t_sess.predicted[size_t(i)] != methods[i])
+                g_staged_n[2]++;
         for (int i = 0; i < nsec; i++) {
             const int m = methods[i];
             if (m <= 0 || m >= FQZ5_M_LAST || t_sess.req_of[i][m] >= 0 || coded_fqz(i, m) ||
@@ -939,9 +1198,10 @@ int fqz5_encode_sections(const fqz5_section *secs, int nsec, const uint32_t *ava
     std::vector<int32_t> ids(nsec), meth(nsec);
     std::vector<uint32_t> ins(nsec);
     for (int i = 0; i < nsec; i++) { ids[i] = secs[i].sec; ins[i] = secs[i].in_size; }
-    // every method of every section in one launch (see sections.encode_run)
+    // every method of every trial section in one launch, the trial's pick
+    // for the others (see sections.encode_run)
     for (int i = 0; i < nsec; i++) masks[i] = avail[secs[i].sec];
-    if (fqz5_sections_try(secs, nsec, masks.data(), sizes.data())) return -1;
+    if (fqz5_sections_try_staged(secs, nsec, masks.data(), sizes.data(), avail, st)) return -1;
     fqz5_trial_replay(ids.data(), ins.data(), sizes.data(), nsec, avail, st, meth.data(),
                       nullptr);
     return fqz5_sections_commit(secs, nsec, meth.data(), res);

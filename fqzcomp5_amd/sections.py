@@ -143,6 +143,20 @@ def _load():
                                          C.POINTER(C.c_uint32),
                                          C.POINTER(C.c_uint32)]
         so.fqz5_sections_try.restype = C.c_int
+        # (a library variant of an A/B run, $FQZ5_LIB_VARIANT, may be older
+        # than the staged try: encode_run then keeps the plain one)
+        if hasattr(so, "fqz5_sections_try_staged"):
+            so.fqz5_sections_try_staged.argtypes = [C.POINTER(Section), C.c_int,
+                                                    C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                                    C.POINTER(C.c_uint32), C.POINTER(TrialState)]
+            so.fqz5_sections_try_staged.restype = C.c_int
+            so.fqz5_staged_plan.argtypes = [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_uint32),
+                                            C.POINTER(TrialState), C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
+            so.fqz5_set_staged_try.restype = C.c_int
+            so.fqz5_set_staged_try.argtypes = [C.c_int]
+            so.fqz5_staged_counts.argtypes = [C.POINTER(C.c_uint64)]
+            so.fqz5_staged_decisions.argtypes = [C.POINTER(C.c_uint64)]
         so.fqz5_trial_replay.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_uint32),
                                          C.POINTER(C.c_uint32), C.c_int,
                                          C.POINTER(C.c_uint32), C.POINTER(TrialState),
@@ -194,16 +208,70 @@ def trial_schedule(sec_ids, avail: np.ndarray, state: TrialState) -> np.ndarray:
     return out
 
 
-def sections_try(secs: list[Section], masks: np.ndarray) -> np.ndarray:
-    """Candidates of masks[i] (per section) for every section."""
+ROLE_TRIAL, ROLE_SETTLED, ROLE_FOLLOW, ROLE_OTHER = range(4)
+
+
+def staged_plan(sec_ids, avail: np.ndarray, state: TrialState):
+    """fqz5_staged_plan: per section (file order) its role in a staged try,
+    the methods the walk gives it and its trial window's index (state
+    unchanged)."""
+    so = _load()
+    ids = np.ascontiguousarray(sec_ids, np.int32)
+    av = np.ascontiguousarray(avail, np.uint32)
+    roles = np.zeros(len(ids), np.int32)
+    out = np.zeros(len(ids), np.uint32)
+    win = np.zeros(len(ids), np.int32)
+    so.fqz5_staged_plan(ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids),
+                        av.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(state),
+                        roles.ctypes.data_as(C.POINTER(C.c_int32)),
+                        out.ctypes.data_as(C.POINTER(C.c_uint32)),
+                        win.ctypes.data_as(C.POINTER(C.c_int32)))
+    return roles, out, win
+
+
+def set_staged_try(on: bool) -> bool:
+    """fqz5_set_staged_try; returns the previous setting."""
+    return bool(_load().fqz5_set_staged_try(1 if on else 0))
+
+
+def staged_counts() -> tuple[int, int, int, int]:
+    """(candidates coded in a first stage, follow sections coded with a
+    provisional pick, picks the commit overturned, candidates skipped) over
+    the staged tries since the library was loaded."""
+    out = (C.c_uint64 * 4)()
+    _load().fqz5_staged_counts(out)
+    return tuple(int(x) for x in out)
+
+
+def staged_decisions() -> list[int]:
+    """Provisional picks made so far, per section kind."""
+    out = (C.c_uint64 * 4)()
+    _load().fqz5_staged_decisions(out)
+    return [int(x) for x in out]
+
+
+def sections_try(secs: list[Section], masks: np.ndarray, state: TrialState | None = None,
+                 avail: np.ndarray | None = None) -> np.ndarray:
+    """Candidates of masks[i] (per section) for every section.  With `state`
+    (the trial state before the first section) and `avail`, the staged try
+    (fqz5_sections_try_staged): the caller holds the whole input from that
+    state on."""
     so = _load()
     sizes = np.zeros(len(secs) * M_LAST, np.uint32)
     av = np.ascontiguousarray(masks, np.uint32)
     assert len(av) == len(secs)
     _lib.after_torch()
-    rc = so.fqz5_sections_try(_arr(Section, secs), len(secs),
-                              av.ctypes.data_as(C.POINTER(C.c_uint32)),
-                              sizes.ctypes.data_as(C.POINTER(C.c_uint32)))
+    if state is not None:
+        avl = np.ascontiguousarray(avail, np.uint32)
+        rc = so.fqz5_sections_try_staged(_arr(Section, secs), len(secs),
+                                         av.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                         sizes.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                         avl.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                         C.byref(state))
+    else:
+        rc = so.fqz5_sections_try(_arr(Section, secs), len(secs),
+                                  av.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                  sizes.ctypes.data_as(C.POINTER(C.c_uint32)))
     if rc:
         raise _lib.NativeError("fqz5_sections_try: " + _lib.last_error())
     return sizes.reshape(len(secs), M_LAST)
@@ -230,14 +298,15 @@ def trial_replay(sec_ids, in_sizes, sizes: np.ndarray, avail: np.ndarray,
     return out
 
 
-def sections_try_bounds(secs: list[Section], masks: np.ndarray):
+def sections_try_bounds(secs: list[Section], masks: np.ndarray, state: TrialState | None = None,
+                        avail: np.ndarray | None = None):
     """sections_try with every fqz / sequence-model candidate's range chain
     skipped (fqz5_set_trial_bounds): (lower, upper) size matrices, equal
     wherever the size is exact."""
     so = _load()
     prev = so.fqz5_set_trial_bounds(1)
     try:
-        lo = sections_try(secs, masks)
+        lo = sections_try(secs, masks, state, avail)
     finally:
         so.fqz5_set_trial_bounds(prev)
     hi = np.zeros(len(secs) * M_LAST, np.uint32)
@@ -532,12 +601,18 @@ def encode_run(secs: list[Section], avail: np.ndarray, state: TrialState,
                bounds: bool = False):
     """try -> (exchange) -> replay -> commit for this rank's sections.
 
-    speculate: every section tries every method in one GPU launch.  A launch
-    lasts as long as its longest rANS chain, so the extra candidates cost
-    little, while encoding the non-trial sections after the replay would add
-    a second chain-length launch.  speculate=False tries only the sections
-    the schedule names (trial and re-trial blocks) and encodes the others
-    once at commit, for candidates that do cost in proportion to their work.
+    speculate: the whole call is one try session.  On one rank that holds
+    the whole input from `state` on, the session is staged
+    (fqz5_sections_try_staged): the long rANS chains run on host cores, one
+    core each, so a candidate nobody reads costs a core for its whole length;
+    only the trial sections code every method, and the others code the
+    trial's pick as soon as the window's sizes are known, beside the helpers
+    still at work (the replay below stays the authority, and the commit codes
+    late what it overturns).  Several ranks keep every rANS method of every
+    section speculative (rank r > 0 would need rank 0's sizes first).
+    speculate=False tries only the sections the schedule names (trial and
+    re-trial blocks) and encodes the others once at commit, serially after
+    the replay.
 
     prune: fqz and sequence-model candidates that provably cannot win the
     trial skip their range chain (fqz5_set_trial_prune), when this rank holds
@@ -557,6 +632,9 @@ def encode_run(secs: list[Section], avail: np.ndarray, state: TrialState,
     # name candidates are speculative too: their host tokenising runs on a
     # helper thread beside the rANS batch, and none is left for commit
     SPEC = RANS_MASK | NAME_MASK
+    staged = state if speculate and _one_rank(group) and \
+        hasattr(_load(), "fqz5_sections_try_staged") and \
+        bounds_usable(ids, (), state, final=True) else None
     if speculate and not (av & WORK_MASK).any():
         masks = av[ids]
         prune = False
@@ -565,9 +643,10 @@ def encode_run(secs: list[Section], avail: np.ndarray, state: TrialState,
         _, _, g_ids0, off = exchange_sizes(blank, ins, ids, group)
         sched_all = trial_schedule(g_ids0, avail, state)
         sched = sched_all[off:off + len(secs)]
-        # rANS candidates stay speculative (chain-bound, nearly free in one
-        # launch); fqz candidates cost in proportion to their work, so only
-        # the scheduled trial sections try them.  So does TLZP3 here: its lzp
+        # rANS candidates stay in the session's masks (a staged try codes
+        # the trial's pick only outside the trial windows); fqz candidates
+        # cost in proportion to their work, so only the scheduled trial
+        # sections try them.  So does TLZP3 here: its lzp
         # pass and order-5 chain over every block's names ended after the
         # tokenisers, the names helper's long pole at -5 (a block after the
         # trial codes it at commit if it wins)
@@ -585,7 +664,7 @@ def encode_run(secs: list[Section], avail: np.ndarray, state: TrialState,
                 bounds_usable(g_ids0, sched_all, state, final=True):
             global last_bounds_decided
             state0 = _copy_state(state)
-            lo, hi = sections_try_bounds(secs, masks)
+            lo, hi = sections_try_bounds(secs, masks, staged, av)
             tried = np.zeros(len(secs), np.uint32)
             meth_all = trial_replay(ids, ins, lo, avail, state, tried)
             last_bounds_decided = trial_decided(lo, hi, ids, ins, tried, sched_all, state0,
@@ -596,7 +675,7 @@ def encode_run(secs: list[Section], avail: np.ndarray, state: TrialState,
     so = _load()
     prev = so.fqz5_set_trial_prune(1 if prune else 0)
     try:
-        local = sections_try(secs, masks)
+        local = sections_try(secs, masks, staged, av)
     finally:
         so.fqz5_set_trial_prune(prev)
     g_sizes, g_ins, g_ids, off = exchange_sizes(local, ins, ids, group)
@@ -743,6 +822,15 @@ def encode_run_bounded(secs: list[Section], avail: np.ndarray, state: TrialState
         sections_try(part, np.zeros(len(ch), np.uint32))    # an empty session
         res += sections_commit(part, meth[ch])
     return res, meth_all, g_sizes, tried, off
+
+
+def _one_rank(group) -> bool:
+    """No other rank shares the call's exchanges (exchange_sizes takes a
+    missing group as the default group, all ranks)."""
+    import torch.distributed as dist
+    if not dist.is_available() or not dist.is_initialized():
+        return True
+    return dist.get_world_size(dist.group.WORLD if group is None else group) == 1
 
 
 def _world(group):

@@ -104,6 +104,49 @@ void fqz5_trial_replay(const int32_t *sec_ids, const uint32_t *in_sizes,
 int fqz5_sections_commit(const fqz5_section *secs, int n, const int32_t *methods,
                          fqz5_section_result *res);
 
+/* The staged try: fqz5_sections_try for a caller that holds the trial state
+ * `st` as it stands before the call's first section (not modified) and the
+ * whole input from there on.  A sequence or quality section outside a trial
+ * window codes one method instead of every method of masks[i]:
+ *   trial    the schedule gives it every method: coded as by fqz5_sections_try;
+ *   settled  the state already holds the pick of its kind (a later window of
+ *            a file, a call with a carried state): that method only;
+ *   follow   its method is the pick of a trial window whose remaining
+ *            sections all lie earlier in this call: it waits until that
+ *            window's rANS candidates have sizes, and is then coded with the
+ *            pick over those sizes (the first smallest (csize + 1) / usize),
+ *            beside the helpers that are still at work.
+ * Name sections code masks[i] as before.  The pick is provisional, the replay
+ * decides: when LZP3, an fqz or a sequence-model candidate wins the window
+ * after all, fqz5_sections_commit codes the section late, as it codes any
+ * method the session lacks.  Output bytes never depend on the staging.  A
+ * candidate that was not coded reports UINT32_MAX.  With staged tries off
+ * (fqz5_set_staged_try(0), or $FQZ5_STAGED_TRY=0) it is fqz5_sections_try. */
+#define FQZ5_ROLE_TRIAL 0
+#define FQZ5_ROLE_SETTLED 1
+#define FQZ5_ROLE_FOLLOW 2
+#define FQZ5_ROLE_OTHER 3         /* names, lengths: not staged */
+int fqz5_sections_try_staged(const fqz5_section *secs, int n, const uint32_t *masks,
+                             uint32_t *sizes, const uint32_t *avail,
+                             const fqz5_trial_state *st);
+/* Host only, the staged try's walk: per section its role, the methods the
+ * walk gives it (avail[sec] in trial sections, the state's pick in settled
+ * ones, 0 in follow ones and outside the trial of the other kinds) and for
+ * trial and follow sections the index of their trial window among the
+ * windows of their kind in this call (else -1). */
+void fqz5_staged_plan(const int32_t *sec_ids, int n, const uint32_t *avail,
+                      const fqz5_trial_state *st, int32_t *roles_out, uint32_t *masks_out,
+                      int32_t *window_out);
+/* Returns the previous setting. */
+int fqz5_set_staged_try(int on);
+/* Since the library was loaded, over staged tries: {candidates coded in a
+ * first stage, follow sections coded with a provisional pick, provisional
+ * picks the commit's methods overturned, candidates of masks[] not coded}. */
+void fqz5_staged_counts(uint64_t out[4]);
+/* Per section kind, the provisional picks made (one per trial window with
+ * follow sections). */
+void fqz5_staged_decisions(uint64_t out[FQZ5_SEC_LAST]);
+
 /* Trial pruning (off by default).  When on, fqz5_sections_try skips the
  * range chain and bytes of an fqz candidate whose size is provably not below
  * the best rANS candidate: its lower bound 8 P >= sum log2(total/freq) - 8
