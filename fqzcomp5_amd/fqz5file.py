@@ -1439,110 +1439,168 @@ def _parse_checked(data, buf, ranges):
     return views, lens, fasta
 
 
-def _decode(data, buf, plus_name: bool, device: str, pairs: bool = False, ranges=None,
-            slices=None, with_qual: bool = True):
-    """Blocks of a .fqz5 (host view `data`, device copy `buf`; `ranges` the
-    block byte ranges within them, all blocks of the file by default) ->
-    the FASTQ text of every block in one device buffer; pairs: (the R1
-    text, the R2 text) of output_fastq_deinterleaved (fqzcomp5.c:3612-3676),
-    even records of every block to R1 and odd ones to R2.
+def _group(items, size_of, wb: int) -> list[list]:
+    """`items` in order, in groups of at most `wb` bytes by size_of(item): an
+    item joins the current group unless that group has items and would pass
+    `wb` with it, so an item larger than `wb` stands alone."""
+    groups, cur, tot = [], [], 0
+    for it in items:
+        z = size_of(it)
+        if cur and tot + z > wb:
+            groups.append(cur)
+            cur, tot = [], 0
+        cur.append(it)
+        tot += z
+    if cur:
+        groups.append(cur)
+    return groups
 
-    slices: per block (rec_first, rec_count), the records whose text is
-    wanted (extract_file): every block is still decoded whole, and its text
-    is laid out by fqz5_fastq_format_range for those records only.
-    with_qual False: the quality sections are not decoded and the text is
-    output_fasta's ('>' name, sequence)."""
-    import contextlib
+
+class _ReadWindow:
+    """Adjacent blocks of a container as read and uploaded together: the host
+    view `data`, its device copy `buf`, the blocks' byte ranges within them
+    (`ranges`, a Blocks) and their numbers in the file (`blocks`, windows of
+    the index).  parse() adds what _parse_checked gives: `views`, `lens`,
+    `fasta`."""
+
+    def __init__(self, data, buf, ranges, blocks=None):
+        self.data, self.buf, self.ranges, self.blocks = data, buf, ranges, blocks
+        self.base = buf.data_ptr()
+
+    def parse(self) -> None:
+        """_parse_checked of the window.  A call of its own, so that its time
+        (the block parse, the CRCs) falls into the stage the caller is in."""
+        self.views, self.lens, self.fasta = _parse_checked(self.data, self.buf, self.ranges)
+        self.rls = [ln.ctypes.data_as(C.POINTER(C.c_uint32)) for ln in self.lens]
+
+    def field(self, j: int, sec: int):
+        """(offset in block j, compressed size, decoded size) of its section `sec`."""
+        v = self.views[j]
+        return {S.SEC_NAME: (v.name_off, v.name_size, v.name_ulen),
+                S.SEC_SEQ: (v.seq_off, v.seq_size, v.seq_ulen),
+                S.SEC_QUAL: (v.qual_off, v.qual_size, v.qual_ulen)}[sec]
+
+    def section(self, j: int, sec: int, dst: int, bases=None):
+        """The section `sec` of block j to decode to the device address `dst`;
+        bases: for SEC_QUAL the block's decoded bases, which the quality
+        decoder reads."""
+        off, size, ulen = self.field(j, sec)
+        return S.Section(self.base + self.ranges[j][0] + off, dst, size, ulen, 0, sec, self.rls[j],
+                         None, len(self.lens[j]), bases)
+
+    def decode(self, secs) -> None:
+        if any(r.status != 0 for r in S.decode(secs)):
+            raise _lib.NativeError("section decoding failed: " + _lib.last_error())
+
+    def release(self) -> None:
+        self.data = self.buf = None
+
+
+def _layout(fmts, pairs: bool, device: str):
+    """The text of blocks laid out one after the other in one device buffer,
+    in two passes over fmts, per block a callable fmt(out, cap) -> (the text's
+    size, the size of its R1 part): the sizes (out None), then the text into
+    the one buffer.  Returns (the text,), with pairs (the R1 text, the R2
+    text) of output_fastq_deinterleaved (fqzcomp5.c:3612-3676)."""
     import torch
-    so = _load()
-    # (the range path's $FQZ5_FILE_TRACE stages; whole-file callers time the call)
-    st_dec = _stage("decode") if slices is not None else contextlib.nullcontext()
-    st_fmt = _stage("format") if slices is not None else contextlib.nullcontext()
-    st_dec.__enter__()
-    if ranges is None:
-        ranges = _blocks_of(data)
-    if not ranges:
-        return torch.empty(0, dtype=torch.uint8, device=device)
-    views, lens, fasta = _parse_checked(data, buf, ranges)
-    nsz = [v.name_ulen for v in views]
-    ssz = [v.seq_ulen for v in views]
+    sizes = [fmt(None, 0) for fmt in fmts]
+    text = torch.empty(max(sum(z for z, _ in sizes), 1), dtype=torch.uint8, device=device)
+    _lib.after_torch(device)
+    at, r1, r2 = 0, [], []
+    for fmt, (z, k) in zip(fmts, sizes):
+        fmt(text.data_ptr() + at, z)
+        r1.append((at, at + k))
+        r2.append((at + k, at + z))
+        at += z
+    if not pairs:
+        return (text[:at],)
+    cat = lambda rs: torch.cat([text[x:y] for x, y in rs]) if rs else text[:0]
+    return cat(r1), cat(r2)
+
+
+def _decode_blocks(win, with_qual: bool, device: str):
+    """Every block of the parsed window decoded into one device buffer, per
+    block its names, bases and (unless FASTA or with_qual False) qualities:
+    (the buffer, per block the three offsets in it)."""
+    import torch
+    nsz = [v.name_ulen for v in win.views]
+    ssz = [v.seq_ulen for v in win.views]
     out_d = torch.empty(sum(nsz) + 2 * sum(ssz) + 1, dtype=torch.uint8, device=device)
     secs, places = [], []
-    o = 0
-    base = buf.data_ptr()
-    for (s, e), v, ln, fa in zip(ranges, views, lens, fasta):
-        rl = ln.ctypes.data_as(C.POINTER(C.c_uint32))
+    o = out_d.data_ptr()
+    for j, (v, fa) in enumerate(zip(win.views, win.fasta)):
         po = (o, o + v.name_ulen, o + v.name_ulen + v.seq_ulen)
-        secs.append(S.Section(base + s + v.name_off, out_d.data_ptr() + po[0], v.name_size,
-                              v.name_ulen, 0, S.SEC_NAME, rl, None, len(ln), None))
-        secs.append(S.Section(base + s + v.seq_off, out_d.data_ptr() + po[1], v.seq_size,
-                              v.seq_ulen, 0, S.SEC_SEQ, rl, None, len(ln), None))
+        secs.append(win.section(j, S.SEC_NAME, po[0]))
+        secs.append(win.section(j, S.SEC_SEQ, po[1]))
         if not fa and with_qual:
-            secs.append(S.Section(base + s + v.qual_off, out_d.data_ptr() + po[2], v.qual_size,
-                                  v.qual_ulen, 0, S.SEC_QUAL, rl, None, len(ln),
-                                  out_d.data_ptr() + po[1]))
+            secs.append(win.section(j, S.SEC_QUAL, po[2], po[1]))
+        else:
+            po = (po[0], po[1], None)
         places.append(po)
-        o = po[2] + v.seq_ulen
-    res = S.decode(secs)
-    if any(r.status != 0 for r in res):
-        raise _lib.NativeError("section decoding failed: " + _lib.last_error())
-    st_dec.__exit__(None, None, None)
-    st_fmt.__enter__()
-    # the text of every block, one after the other in one device buffer
-    fmt = so.fqz5_fastq_format_pairs if pairs else so.fqz5_fastq_format
-    if slices is not None:
-        def fmt(*a):                      # a[6]: the block's (rec_first, rec_count)
-            return so.fqz5_fastq_format_range(*a[:6], *a[6], int(plus_name), int(pairs), *a[7:10],
-                                              a[10] if pairs else None)
-    args, sizes, r1 = [], [], []
-    for j, (v, ln, po, fa) in enumerate(zip(views, lens, places, fasta)):
-        size, s1 = C.c_uint64(0), C.c_uint64(0)
-        a = (out_d.data_ptr() + po[0], v.name_ulen, out_d.data_ptr() + po[1],
-             None if fa or not with_qual else out_d.data_ptr() + po[2], ln.ctypes.data, len(ln),
-             int(plus_name) if slices is None else slices[j])
-        _check(fmt(*a, None, 0, C.byref(size), *((C.byref(s1),) if pairs else ())),
-               "fqz5_fastq_format")
-        args.append(a)
-        sizes.append(int(size.value))
-        r1.append(int(s1.value))
-    text = torch.empty(max(sum(sizes), 1), dtype=torch.uint8, device=device)
-    _lib.after_torch(device)
-    at = 0
-    for a, n in zip(args, sizes):
-        size, s1 = C.c_uint64(0), C.c_uint64(0)
-        _check(fmt(*a, text.data_ptr() + at, n, C.byref(size),
-                   *((C.byref(s1),) if pairs else ())), "fqz5_fastq_format")
-        at += n
-    st_fmt.__exit__(None, None, None)
-    if not pairs:
-        return text[:at]
-    idx1, idx2, at = [], [], 0
-    for n, k in zip(sizes, r1):
-        idx1.append((at, at + k))
-        idx2.append((at + k, at + n))
-        at += n
-    cat = lambda rs: torch.cat([text[a:b] for a, b in rs]) if rs else text[:0]
-    return cat(idx1), cat(idx2)
+        o += v.name_ulen + 2 * v.seq_ulen
+    win.decode(secs)
+    return out_d, places
+
+
+def _format_blocks(win, places, plus_name: bool, device: str, pairs: bool, slices):
+    """The text of the window's decoded blocks (`places`: _decode_blocks'),
+    see _decode."""
+    so = _load()
+
+    def fmt_of(j):
+        head = (places[j][0], win.views[j].name_ulen, places[j][1], places[j][2],
+                win.lens[j].ctypes.data, len(win.lens[j]))
+
+        def fmt(out, cap):
+            size, s1 = C.c_uint64(0), C.c_uint64(0)
+            if slices is not None:
+                rc = so.fqz5_fastq_format_range(*head, *slices[j], int(plus_name), int(pairs), out,
+                                                cap, C.byref(size), C.byref(s1) if pairs else None)
+            elif pairs:
+                rc = so.fqz5_fastq_format_pairs(*head, int(plus_name), out, cap, C.byref(size),
+                                                C.byref(s1))
+            else:
+                rc = so.fqz5_fastq_format(*head, int(plus_name), out, cap, C.byref(size))
+            _check(rc, "fqz5_fastq_format")
+            return int(size.value), int(s1.value)
+        return fmt
+    return _layout([fmt_of(j) for j in range(len(win.views))], pairs, device)
+
+
+def _decode(win, plus_name: bool, device: str, pairs: bool = False):
+    """The blocks of a parsed window -> (the FASTQ text of every block in one
+    device buffer,); pairs: (the R1 text, the R2 text), even records of every
+    block to R1 and odd ones to R2.  (The whole-file callers, which time the
+    call; the range path records its stages around the two steps.)"""
+    out_d, places = _decode_blocks(win, True, device)
+    return _format_blocks(win, places, plus_name, device, pairs, None)
+
+
+def _whole(data, device: str):
+    """A container held in memory as one parsed window, None without blocks."""
+    import torch
+    ranges = _blocks_of(data)
+    if not ranges:
+        return None
+    win = _ReadWindow(data, torch.frombuffer(bytearray(data), dtype=torch.uint8).to(device), ranges)
+    win.parse()
+    return win
 
 
 def decompress_bytes(data: bytes, plus_name: bool = False, device: str = "cuda") -> bytes:
     """fqzcomp5 -d of a .fqz5 (its blocks parsed, CRC-checked and decoded on
     the GPU, the FASTQ text formatted there)."""
-    import torch
-    if not _blocks_of(data):
-        return b""
-    buf = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(device)
-    return _decode(data, buf, plus_name, device).cpu().numpy().tobytes()
+    win = _whole(data, device)
+    return _decode(win, plus_name, device)[0].cpu().numpy().tobytes() if win else b""
 
 
 def decompress_paired_bytes(data: bytes, plus_name: bool = False,
                             device: str = "cuda") -> tuple[bytes, bytes]:
     """fqzcomp5 -d in out1 out2: the records deinterleaved into R1 / R2."""
-    import torch
-    if not _blocks_of(data):
+    win = _whole(data, device)
+    if not win:
         return b"", b""
-    buf = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(device)
-    t1, t2 = _decode(data, buf, plus_name, device, pairs=True)
+    t1, t2 = _decode(win, plus_name, device, pairs=True)
     return t1.cpu().numpy().tobytes(), t2.cpu().numpy().tobytes()
 
 
@@ -1636,40 +1694,30 @@ def decompress_file(src: str, dst: str, plus_name: bool = False, device: str = "
                 ranges = _file_blocks(f, size)
             nb = len(ranges)
             mine = [b for b in range(nb) if (b * ws) // max(nb, 1) == rk] if nb else []
-            wb = window_bytes or DEFAULT_WINDOW
-            groups, cur, tot = [], [], 0
-            for b in mine:
-                z = ranges[b][1] - ranges[b][0]
-                if cur and tot + z > wb:
-                    groups.append(cur)
-                    cur, tot = [], 0
-                cur.append(b)
-                tot += z
-            if cur:
-                groups.append(cur)
+            groups = _group(mine, lambda b: ranges[b][1] - ranges[b][0],
+                            window_bytes or DEFAULT_WINDOW)
             gz = [d.endswith(".gz") for d in outs]
             streams, sinks, at = [], [], 0
             plain = []                        # single process: plain outputs by positioned writes
-            st_open = _stage("open")
-            st_open.__enter__()
-            if single:
-                import gzip
-                streams = [gzip.GzipFile(filename="", mode="wb", compresslevel=6, mtime=0,
-                                         fileobj=open(d, "wb")) if z else None
-                           for d, z in zip(outs, gz)]
-                plain = [None if z else _Sink(d, True) for d, z in zip(outs, gz)]
-            elif spill:
-                streams = [open(f"{d}.part{rk}", "wb") for d in outs]
-            else:
-                # one output: every block's text size from its headers, so this
-                # rank's text starts at the sum over the blocks before its first
-                sizes = [_block_text_size(f, s, e, plus_name, ranges.version) for s, e in ranges]
-                at = sum(sizes[:mine[0]]) if mine else 0
-                if rk == 0:
-                    _Sink(dst, True).close()
-                _barrier(group)
-                sinks = [_Sink(dst, False)]
-            st_open.__exit__()
+            with _stage("open"):
+                if single:
+                    import gzip
+                    streams = [gzip.GzipFile(filename="", mode="wb", compresslevel=6, mtime=0,
+                                             fileobj=open(d, "wb")) if z else None
+                               for d, z in zip(outs, gz)]
+                    plain = [None if z else _Sink(d, True) for d, z in zip(outs, gz)]
+                elif spill:
+                    streams = [open(f"{d}.part{rk}", "wb") for d in outs]
+                else:
+                    # one output: every block's text size from its headers, so this
+                    # rank's text starts at the sum over the blocks before its first
+                    sizes = [_block_text_size(f, s, e, plus_name, ranges.version)
+                             for s, e in ranges]
+                    at = sum(sizes[:mine[0]]) if mine else 0
+                    if rk == 0:
+                        _Sink(dst, True).close()
+                    _barrier(group)
+                    sinks = [_Sink(dst, False)]
             written = [0 for _ in outs]
             try:
                 for gb in groups:
@@ -1688,49 +1736,45 @@ def decompress_file(src: str, dst: str, plus_name: bool = False, device: str = "
                     with _stage("upload"):
                         buf = host.to(device)      # blocking: block parsing runs on the library's streams
                     with _stage("decode"):
-                        texts = _decode(hv, buf, plus_name, device, pairs=dst2 is not None,
-                                        ranges=Blocks([(ranges[b][0] - a, ranges[b][1] - a)
+                        win = _ReadWindow(hv, buf, Blocks([(ranges[b][0] - a, ranges[b][1] - a)
                                                        for b in gb], ranges.version))
-                    if dst2 is None:
-                        texts = (texts,)
+                        win.parse()
+                        texts = _decode(win, plus_name, device, pairs=dst2 is not None)
                     for j, t in enumerate(texts):
                         with _stage("download"):
                             out = _pinned(int(t.numel()))
                             out.copy_(t)
-                        st_w = _stage("write")
-                        st_w.__enter__()
-                        if sinks:
-                            want = sum(sizes[b] for b in gb)
-                            if int(t.numel()) != want:
-                                raise _lib.NativeError("decoded text size differs from the block headers'")
-                            sinks[j].write_at(at + written[j], out.numpy())
-                        elif plain and plain[j] is not None:
-                            plain[j].write_at(written[j], out.numpy())
-                        else:
-                            streams[j].write(memoryview(out.numpy()))
-                        written[j] += int(t.numel())
-                        st_w.__exit__()
+                        with _stage("write"):
+                            if sinks:
+                                want = sum(sizes[b] for b in gb)
+                                if int(t.numel()) != want:
+                                    raise _lib.NativeError(
+                                        "decoded text size differs from the block headers'")
+                                sinks[j].write_at(at + written[j], out.numpy())
+                            elif plain and plain[j] is not None:
+                                plain[j].write_at(written[j], out.numpy())
+                            else:
+                                streams[j].write(memoryview(out.numpy()))
+                            written[j] += int(t.numel())
                         del out
                     with _stage("free"):
-                        del buf, host, texts
+                        del buf, host, texts, win
             finally:
-                st_close = _stage("close")
-                st_close.__enter__()
-                for sk in plain:
-                    if sk is not None:
+                with _stage("close"):
+                    for sk in plain:
+                        if sk is not None:
+                            sk.close()
+                    for st in streams:
+                        if st is None:
+                            continue
+                        if isinstance(st, __import__("gzip").GzipFile):
+                            raw = st.fileobj          # (close() drops the reference)
+                            st.close()
+                            raw.close()
+                        else:
+                            st.close()
+                    for sk in sinks:
                         sk.close()
-                for st in streams:
-                    if st is None:
-                        continue
-                    if isinstance(st, __import__("gzip").GzipFile):
-                        raw = st.fileobj          # (close() drops the reference)
-                        st.close()
-                        raw.close()
-                    else:
-                        st.close()
-                for sk in sinks:
-                    sk.close()
-                st_close.__exit__()
         _trace_dump("decode")
         if single:
             return sum(written)
@@ -1818,6 +1862,20 @@ def _reader(src):
     return _PosBytes(src), False
 
 
+def _run(opened, what: str, fn):
+    """fn(reader) for `opened`, a (reader, whether to close it) as _reader
+    gives: the reader closed behind it, then the $FQZ5_FILE_TRACE line of the
+    entry point `what`."""
+    rd, close = opened
+    try:
+        res = fn(rd)
+    finally:
+        if close:
+            rd.close()
+    _trace_dump(what)
+    return res
+
+
 def read_index(src) -> Index:
     """The blocks of a .fqz5 (a path, the file's bytes, or a positioned
     reader) as an Index.  With an index offset in the header this is one
@@ -1901,43 +1959,62 @@ def _check_entry(index, b: int, hv, a: int) -> None:
             f"size {t - s - 4} records {n} in the index")
 
 
-def _extract_windows(rd, first: int, count: int, plus_name: bool, device: str, pairs: bool,
-                     with_qual: bool, window_bytes: int | None):
-    """The text of records [first, first + count) (pairs: of pairs) of the
-    container behind `rd`, window by window: device tensors (pairs: the R1
-    and the R2 text)."""
+def _windows(rd, index, groups, device: str):
+    """The blocks of the container behind `rd`, window by window: per group
+    of `groups` (adjacent block numbers of `index`) one read, the blocks
+    checked against their index entries, one upload; yields the _ReadWindow,
+    unparsed.  One window's host and device buffers are alive at a time: a
+    window is released before the next is read."""
     import torch
-    mul = 2 if pairs else 1
-    with _stage("index"):
-        index = read_index(rd)
-        cov = cover(index, mul * first, mul * count)
-    wb = window_bytes or DEFAULT_WINDOW
-    groups, cur, tot = [], [], 0
-    for c in cov:
-        z = index[c[0]][1] - index[c[0]][0]
-        if cur and tot + z > wb:
-            groups.append(cur)
-            cur, tot = [], 0
-        cur.append(c)
-        tot += z
-    if cur:
-        groups.append(cur)
     for grp in groups:
-        a, e = index[grp[0][0]][0], index[grp[-1][0]][1]      # (covering blocks are adjacent)
+        a, e = index[grp[0]][0], index[grp[-1]][1]
         with _stage("read"):
             hv = rd.read(a, e)
             if len(hv) != e - a:
                 raise _lib.NativeError("index disagrees with the file: a block past its end")
-        for b, _, _ in grp:
+        for b in grp:
             _check_entry(index, b, hv, a)
         with _stage("upload"):
             buf = torch.from_numpy(np.ascontiguousarray(hv)).to(device)   # blocking
-        texts = _decode(hv, buf, plus_name, device, pairs=pairs,
-                        ranges=Blocks([(index[b][0] - a, index[b][1] - a) for b, _, _ in grp],
-                                      index.version),
-                        slices=[(rf, rc) for _, rf, rc in grp], with_qual=with_qual)
-        yield texts if pairs else (texts,)
-        del buf, hv, texts
+        win = _ReadWindow(hv, buf, Blocks([(index[b][0] - a, index[b][1] - a) for b in grp],
+                                      index.version), grp)
+        del hv, buf
+        yield win
+        win.release()
+        del win
+
+
+def _index_windows(rd, index, device: str, window_bytes: int | None):
+    """_windows over every block of the index, at most `window_bytes` each."""
+    groups = _group(range(len(index)), lambda b: index[b][1] - index[b][0],
+                    window_bytes or DEFAULT_WINDOW)
+    return _windows(rd, index, groups, device)
+
+
+def _extract_windows(rd, first: int, count: int, plus_name: bool, device: str, pairs: bool,
+                     with_qual: bool, window_bytes: int | None):
+    """The text of records [first, first + count) (pairs: of pairs) of the
+    container behind `rd`, window by window: device tensors (pairs: the R1
+    and the R2 text).  Every covering block is decoded whole and its text laid
+    out by fqz5_fastq_format_range for the wanted records only; with_qual
+    False: the quality sections are not decoded and the text is
+    output_fasta's ('>' name, sequence)."""
+    mul = 2 if pairs else 1
+    with _stage("index"):
+        index = read_index(rd)
+        cov = cover(index, mul * first, mul * count)
+    groups = _group(cov, lambda c: index[c[0]][1] - index[c[0]][0], window_bytes or DEFAULT_WINDOW)
+    wins = _windows(rd, index, [[b for b, _, _ in grp] for grp in groups], device)
+    for grp, win in zip(groups, wins):
+        with _stage("decode"):
+            win.parse()
+            out_d, places = _decode_blocks(win, with_qual, device)
+        with _stage("format"):
+            texts = _format_blocks(win, places, plus_name, device, pairs,
+                                   [(rf, rc) for _, rf, rc in grp])
+        del out_d
+        yield texts
+        del texts
 
 
 def extract_bytes(data, first: int, count: int, plus_name: bool = False, device: str = "cuda",
@@ -1999,15 +2076,9 @@ def extract_file(src: str, dst: str, first: int, count: int, plus_name: bool = F
     quality section is decoded and the text is FASTA.  A ".gz" destination is
     gzip-compressed.  One process; returns the text bytes written."""
     pairs = dst2 is not None
-    rd = _PosFile(src)
-    try:
-        written = _write_texts([dst] + ([dst2] if pairs else []),
-                               _extract_windows(rd, first, count, plus_name, device, pairs, with_qual,
-                                                window_bytes))
-    finally:
-        rd.close()
-    _trace_dump("extract")
-    return sum(written)
+    return sum(_run((_PosFile(src), True), "extract", lambda rd: _write_texts(
+        [dst] + ([dst2] if pairs else []),
+        _extract_windows(rd, first, count, plus_name, device, pairs, with_qual, window_bytes))))
 
 
 # ---------------------------------------------------------------------------
@@ -2046,18 +2117,26 @@ def read_name_list(path) -> list[bytes]:
         return [x for x in (ln.rstrip(b"\r\n") for ln in f) if x]
 
 
+def _as_bytes(given, what: str):
+    """The caller's names or patterns (`what` names them in errors) one by
+    one as bytes: str ones are UTF-8; an empty one or one with a NUL byte is
+    a ValueError."""
+    for i, x in enumerate(given):
+        b = x.encode() if isinstance(x, str) else bytes(x)
+        if not b:
+            raise ValueError(f"{what} {i} is empty")
+        if b"\0" in b:
+            raise ValueError(f"{what} {i} holds a NUL byte")
+        yield b
+
+
 def _queries(names):
     """The caller's names as (the names as given, the distinct names as
     bytes in order of first occurrence, for each of those the index of that
     first occurrence).  str names are UTF-8; an empty name is a ValueError."""
     given = list(names)
     qs, first, seen = [], [], set()
-    for i, x in enumerate(given):
-        b = x.encode() if isinstance(x, str) else bytes(x)
-        if not b:
-            raise ValueError(f"read name {i} is empty")
-        if b"\0" in b:
-            raise ValueError(f"read name {i} holds a NUL byte")
+    for i, b in enumerate(_as_bytes(given, "read name")):
         if b not in seen:
             seen.add(b)
             qs.append(b)
@@ -2080,8 +2159,26 @@ def _name_hits(given, first, records, qidx, written: int = 0) -> NameHits:
     return NameHits(records, query, missing, written)
 
 
-class _NameTable:
+class _Native:
+    """A handle `p` of the library `so`, freed by its function FREE on close
+    or on leaving the `with`."""
+    p, FREE = None, ""
+
+    def close(self) -> None:
+        if self.p:
+            getattr(self.so, self.FREE)(self.p)
+            self.p = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class _NameTable(_Native):
     """fqz5_name_table of the distinct queries (freed on exit)."""
+    FREE = "fqz5_names_table_free"
 
     def __init__(self, queries: list[bytes], tag_bits: int = 32):
         self.so = _load()
@@ -2092,24 +2189,6 @@ class _NameTable:
 
     def find(self, key: bytes) -> int:
         return int(self.so.fqz5_names_table_find(self.p, key, len(key)))
-
-    def close(self) -> None:
-        if self.p:
-            self.so.fqz5_names_table_free(self.p)
-            self.p = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-
-def _sec_of(v, sec: int):
-    """(offset in the block, compressed size, decoded size) of a section."""
-    return {S.SEC_NAME: (v.name_off, v.name_size, v.name_ulen),
-            S.SEC_SEQ: (v.seq_off, v.seq_size, v.seq_ulen),
-            S.SEC_QUAL: (v.qual_off, v.qual_size, v.qual_ulen)}[sec]
 
 
 def _key_windows(rd, key: int, match, pairs: bool, extract: bool, plus_name: bool,
@@ -2124,60 +2203,38 @@ def _key_windows(rd, key: int, match, pairs: bool, extract: bool, plus_name: boo
     Yields (file record numbers of the window's hits, their query indices, the
     hits' text as device tensors or None without `extract`; pairs: R1 and R2
     text)."""
+    import functools
     import torch
     so = _load()
     with _stage("index"):
         index = read_index(rd)
-    wb = window_bytes or DEFAULT_WINDOW
-    groups, cur, tot = [], [], 0
-    for b, (s, t, _) in enumerate(index):
-        if cur and tot + t - s > wb:
-            groups.append(cur)
-            cur, tot = [], 0
-        cur.append(b)
-        tot += t - s
-    if cur:
-        groups.append(cur)
     rec0 = [0]
     for _, _, n in index:
         rec0.append(rec0[-1] + int(n))            # (Python ints: more than 2^32 records)
-    for grp in groups:
-        a, e = index[grp[0]][0], index[grp[-1]][1]
-        with _stage("read"):
-            hv = rd.read(a, e)
-            if len(hv) != e - a:
-                raise _lib.NativeError("index disagrees with the file: a block past its end")
-        for b in grp:
-            _check_entry(index, b, hv, a)
-        with _stage("upload"):
-            buf = torch.from_numpy(np.ascontiguousarray(hv)).to(device)   # blocking
+    for win in _index_windows(rd, index, device, window_bytes):
         with _stage("names" if key == S.SEC_NAME else "seqs"):
-            ranges = Blocks([(index[b][0] - a, index[b][1] - a) for b in grp], index.version)
-            views, lens, fasta = _parse_checked(hv, buf, ranges)
-            koff = np.concatenate([[0], np.cumsum([_sec_of(v, key)[2]
-                                                   for v in views])]).astype(np.int64)
+            win.parse()
+            views, lens, fasta = win.views, win.lens, win.fasta
+            kulen = [win.field(j, key)[2] for j in range(len(views))]
+            koff = np.concatenate([[0], np.cumsum(kulen)]).astype(np.int64)
             key_d = torch.empty(int(koff[-1]) + 1, dtype=torch.uint8, device=device)
-            base = buf.data_ptr()
-            rls = [ln.ctypes.data_as(C.POINTER(C.c_uint32)) for ln in lens]
             ptr = [{key: key_d.data_ptr() + int(koff[j])} for j in range(len(views))]
 
             def section(j, sec):          # (the quality decoder reads the block's decoded bases)
-                off, size, ulen = _sec_of(views[j], sec)
-                return S.Section(base + ranges[j][0] + off, ptr[j][sec], size, ulen, 0, sec, rls[j],
-                                 None, len(lens[j]), ptr[j][S.SEC_SEQ] if sec == S.SEC_QUAL else None)
-            if any(r.status != 0 for r in S.decode([section(j, key) for j in range(len(views))])):
-                raise _lib.NativeError("section decoding failed: " + _lib.last_error())
+                return win.section(j, sec, ptr[j][sec],
+                                   ptr[j][S.SEC_SEQ] if sec == S.SEC_QUAL else None)
+            win.decode([section(j, key) for j in range(len(views))])
         recs, qidx, sels = [], [], {}
         with _stage("match"):
             hits = torch.empty((2, max(max(len(ln) for ln in lens), 1)), dtype=torch.int32,
                                device=device)
-            for j, (v, ln) in enumerate(zip(views, lens)):
+            for j, ln in enumerate(lens):
                 _lib.after_torch(device)          # (the last block's hits have been copied)
-                n = match(ptr[j][key], _sec_of(v, key)[2], ln, hits)
+                n = match(ptr[j][key], kulen[j], ln, hits)
                 if not n:
                     continue
                 got = hits[:, :n].cpu().numpy().view(np.uint32)      # the compacted hits alone
-                recs.append(got[0].astype(np.uint64) + np.uint64(rec0[grp[j]]))
+                recs.append(got[0].astype(np.uint64) + np.uint64(rec0[win.blocks[j]]))
                 qidx.append(got[1].copy())
                 if extract:
                     sels[j] = hits[0, :n].clone()
@@ -2185,7 +2242,7 @@ def _key_windows(rd, key: int, match, pairs: bool, extract: bool, plus_name: boo
         qidx = np.concatenate(qidx) if qidx else np.zeros(0, np.uint32)
         if not extract:
             yield recs, qidx, None
-            del buf, hv, key_d
+            del key_d
             continue
         with _stage("decode"):
             rest, o = [], 0
@@ -2194,12 +2251,12 @@ def _key_windows(rd, key: int, match, pairs: bool, extract: bool, plus_name: boo
                     if sec == key or (sec == S.SEC_QUAL and (fasta[j] or not with_qual)):
                         continue
                     rest.append((j, sec, o))
-                    o += _sec_of(views[j], sec)[2]
+                    o += win.field(j, sec)[2]
             out_d = torch.empty(o + 1, dtype=torch.uint8, device=device)
             for j, sec, at in rest:
                 ptr[j][sec] = out_d.data_ptr() + at
-            if rest and any(r.status != 0 for r in S.decode([section(j, sec) for j, sec, _ in rest])):
-                raise _lib.NativeError("section decoding failed: " + _lib.last_error())
+            if rest:
+                win.decode([section(j, sec) for j, sec, _ in rest])
         with _stage("format"):
             def fmt(j, out, cap):
                 size, s1 = C.c_uint64(0), C.c_uint64(0)
@@ -2210,22 +2267,9 @@ def _key_windows(rd, key: int, match, pairs: bool, extract: bool, plus_name: boo
                     int(pairs), out, cap, C.byref(size), C.byref(s1)), "fqz5_fastq_format_list")
                 return int(size.value), int(s1.value)
             _lib.after_torch(device)
-            sizes = {j: fmt(j, None, 0) for j in sels}
-            text = torch.empty(max(sum(z for z, _ in sizes.values()), 1), dtype=torch.uint8,
-                               device=device)
-            _lib.after_torch(device)
-            at, r1, r2 = 0, [], []
-            for j, (z, k) in sizes.items():
-                fmt(j, text.data_ptr() + at, z)
-                r1.append((at, at + k))
-                r2.append((at + k, at + z))
-                at += z
-        if not pairs:
-            yield recs, qidx, (text[:at],)
-        else:
-            cat = lambda rs: torch.cat([text[x:y] for x, y in rs]) if rs else text[:0]
-            yield recs, qidx, (cat(r1), cat(r2))
-        del buf, hv, key_d, out_d, text
+            texts = _layout([functools.partial(fmt, j) for j in sels], pairs, device)
+        yield recs, qidx, texts
+        del key_d, out_d, texts
 
 
 def _lookup(rd, key: int, match, pairs, extract, plus_name, with_qual, device, window_bytes, sink):
@@ -2276,14 +2320,18 @@ def find_names(src, names, whole: bool = False, pairs: bool = False, device: str
     record's key is its name up to the first ' ' or '\\t' (kseq's name), with
     `whole` the entire header line; keys are compared byte for byte.  pairs:
     a hit on record 2k or 2k + 1 selects both mates."""
-    rd, close = _reader(src)
-    try:
-        res = _find(rd, names, whole, pairs, False, False, True, device, window_bytes, None)
-    finally:
-        if close:
-            rd.close()
-    _trace_dump("find_names")
-    return res
+    return _run(_reader(src), "find_names", lambda rd: _find(
+        rd, names, whole, pairs, False, False, True, device, window_bytes, None))
+
+
+def _bytes_sink(out: list):
+    """The sink of the extractors to bytes: every window's text appended to
+    `out`; returns the bytes held."""
+    def sink(windows):
+        for (t,) in windows:
+            out.append(t.cpu().numpy().tobytes())
+        return sum(len(x) for x in out)
+    return sink
 
 
 def extract_names_bytes(data, names, whole: bool = False, plus_name: bool = False,
@@ -2292,12 +2340,8 @@ def extract_names_bytes(data, names, whole: bool = False, plus_name: bool = Fals
     file order, as the text decompress_bytes gives for them (with_qual
     False: FASTA text, no quality section decoded).  See find_names."""
     out = []
-
-    def sink(windows):
-        for (t,) in windows:
-            out.append(t.cpu().numpy().tobytes())
-        return sum(len(x) for x in out)
-    _find(_PosBytes(data), names, whole, False, True, plus_name, with_qual, device, None, sink)
+    _find(_PosBytes(data), names, whole, False, True, plus_name, with_qual, device, None,
+          _bytes_sink(out))
     _trace_dump("extract_names")
     return b"".join(out)
 
@@ -2317,14 +2361,9 @@ def extract_names_file(src: str, dst: str, names, whole: bool = False, plus_name
     ".gz" destination is gzip-compressed.  One process; returns the NameHits
     (`written`: the text bytes written)."""
     outs = [dst] + ([dst2] if dst2 is not None else [])
-    rd = _PosFile(src)
-    try:
-        res = _find(rd, names, whole, dst2 is not None, True, plus_name, with_qual, device,
-                    window_bytes, lambda w: sum(_write_texts(outs, w)))
-    finally:
-        rd.close()
-    _trace_dump("extract_names")
-    return res
+    return _run((_PosFile(src), True), "extract_names", lambda rd: _find(
+        rd, names, whole, dst2 is not None, True, plus_name, with_qual, device, window_bytes,
+        lambda w: sum(_write_texts(outs, w))))
 
 
 # ---------------------------------------------------------------------------
@@ -2393,12 +2432,7 @@ def _seq_queries(patterns, revcomp: bool):
     outside ACGTNacgtn is a ValueError."""
     given = list(patterns)
     qs, origin, seen = [], [], set()
-    for i, x in enumerate(given):
-        b = x.encode() if isinstance(x, str) else bytes(x)
-        if not b:
-            raise ValueError(f"pattern {i} is empty")
-        if b"\0" in b:
-            raise ValueError(f"pattern {i} holds a NUL byte")
+    for i, b in enumerate(_as_bytes(given, "pattern")):
         forms = [(b, False)]
         if revcomp:
             if b.translate(None, b"ACGTacgtNn"):
@@ -2427,8 +2461,7 @@ def _seq_hits(given, qs, origin, revcomp: bool, records, qidx, seen, written: in
         reverse[~none] = np.asarray([r for _, r in origin], bool)[at]
     where = {q: k for k, q in enumerate(qs)}
     missing, done = [], set()
-    for x in given:
-        b = x.encode() if isinstance(x, str) else bytes(x)
+    for x, b in zip(given, _as_bytes(given, "pattern")):
         if b in done:
             continue
         done.add(b)
@@ -2438,8 +2471,9 @@ def _seq_hits(given, qs, origin, revcomp: bool, records, qidx, seen, written: in
     return SeqHits(records, query, reverse, missing, written)
 
 
-class _SeqTable:
+class _SeqTable(_Native):
     """fqz5_seq_table of the distinct queries (freed on exit)."""
+    FREE = "fqz5_seqs_table_free"
 
     def __init__(self, queries: list[bytes], tag_bits: int = 32, anchor: int = 0):
         self.so = _load()
@@ -2457,17 +2491,6 @@ class _SeqTable:
         _check(self.so.fqz5_seqs_scan_host(self.p, seq, len(seq), lens.ctypes.data, len(lens),
                                            hit.ctypes.data, seen.ctypes.data), "fqz5_seqs_scan_host")
         return hit, seen
-
-    def close(self) -> None:
-        if self.p:
-            self.so.fqz5_seqs_table_free(self.p)
-            self.p = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
 
 def _find_seqs(rd, patterns, revcomp, pairs, extract, plus_name, with_qual, device, window_bytes,
@@ -2509,15 +2532,8 @@ def find_seqs(src, patterns, revcomp: bool = False, pairs: bool = False, device:
     revcomp: each pattern's reverse complement (A<->T, C<->G, N; other bytes
     are a ValueError) is searched as well.  pairs: a hit on record 2k or
     2k + 1 selects both mates."""
-    rd, close = _reader(src)
-    try:
-        res = _find_seqs(rd, patterns, revcomp, pairs, False, False, True, device, window_bytes,
-                         None)
-    finally:
-        if close:
-            rd.close()
-    _trace_dump("find_seqs")
-    return res
+    return _run(_reader(src), "find_seqs", lambda rd: _find_seqs(
+        rd, patterns, revcomp, pairs, False, False, True, device, window_bytes, None))
 
 
 def extract_seqs_bytes(data, patterns, revcomp: bool = False, plus_name: bool = False,
@@ -2527,13 +2543,8 @@ def extract_seqs_bytes(data, patterns, revcomp: bool = False, plus_name: bool = 
     (with_qual False: FASTA text, no quality section decoded).  See
     find_seqs."""
     out = []
-
-    def sink(windows):
-        for (t,) in windows:
-            out.append(t.cpu().numpy().tobytes())
-        return sum(len(x) for x in out)
     _find_seqs(_PosBytes(data), patterns, revcomp, False, True, plus_name, with_qual, device, None,
-               sink)
+               _bytes_sink(out))
     _trace_dump("extract_seqs")
     return b"".join(out)
 
@@ -2553,14 +2564,9 @@ def extract_seqs_file(src: str, dst: str, patterns, revcomp: bool = False, plus_
     ".gz" destination is gzip-compressed.  One process; returns the SeqHits
     (`written`: the text bytes written)."""
     outs = [dst] + ([dst2] if dst2 is not None else [])
-    rd = _PosFile(src)
-    try:
-        res = _find_seqs(rd, patterns, revcomp, dst2 is not None, True, plus_name, with_qual,
-                         device, window_bytes, lambda w: sum(_write_texts(outs, w)))
-    finally:
-        rd.close()
-    _trace_dump("extract_seqs")
-    return res
+    return _run((_PosFile(src), True), "extract_seqs", lambda rd: _find_seqs(
+        rd, patterns, revcomp, dst2 is not None, True, plus_name, with_qual, device, window_bytes,
+        lambda w: sum(_write_texts(outs, w))))
 
 
 # ---------------------------------------------------------------------------
@@ -2613,8 +2619,9 @@ def _stats_host(seq: bytes, qual, lens, cycles: int, mates: int, out=None, per_r
     return out, qs, gc
 
 
-class _StatsAcc:
+class _StatsAcc(_Native):
     """fqz5_stats, the device accumulator (freed on exit)."""
+    FREE = "fqz5_stats_free"
 
     def __init__(self, cycles: int, mates: int):
         self.so = _load()
@@ -2633,17 +2640,6 @@ class _StatsAcc:
         out = np.zeros(int(self.so.fqz5_stats_words(self.cycles, self.mates)), np.uint64)
         _check(self.so.fqz5_stats_read(self.p, out.ctypes.data, len(out)), "fqz5_stats_read")
         return out
-
-    def close(self) -> None:
-        if self.p:
-            self.so.fqz5_stats_free(self.p)
-            self.p = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
 
 def _merge_lengths(a, b):
@@ -2698,49 +2694,25 @@ def _stats(rd, cycles: int, mates: int, per_record: bool, device: str, window_by
     import torch
     with _stage("index"):
         index = read_index(rd)
-    wb = window_bytes or DEFAULT_WINDOW
-    groups, cur, tot = [], [], 0
-    for b, (s, t, _) in enumerate(index):
-        if cur and tot + t - s > wb:
-            groups.append(cur)
-            cur, tot = [], 0
-        cur.append(b)
-        tot += t - s
-    if cur:
-        groups.append(cur)
     none = (np.zeros(0, np.uint32), np.zeros(0, np.uint64))
     lengths = [none] * mates
     rlen, rgc, rqs = [], [], []
     with _StatsAcc(cycles, mates) as acc:
-        for grp in groups:
-            a, e = index[grp[0]][0], index[grp[-1]][1]
-            with _stage("read"):
-                hv = rd.read(a, e)
-                if len(hv) != e - a:
-                    raise _lib.NativeError("index disagrees with the file: a block past its end")
-            for b in grp:
-                _check_entry(index, b, hv, a)
-            with _stage("upload"):
-                buf = torch.from_numpy(np.ascontiguousarray(hv)).to(device)   # blocking
+        for win in _index_windows(rd, index, device, window_bytes):
             with _stage("decode"):
-                ranges = Blocks([(index[b][0] - a, index[b][1] - a) for b in grp], index.version)
-                views, lens, fasta = _parse_checked(hv, buf, ranges)
+                win.parse()
+                views, lens, fasta = win.views, win.lens, win.fasta
                 # per block its bases, then (unless FASTA) its qualities
                 at = np.concatenate([[0], np.cumsum([v.seq_ulen * (1 if fa else 2)
                                                      for v, fa in zip(views, fasta)])])
                 out_d = torch.empty(int(at[-1]) + 1, dtype=torch.uint8, device=device)
-                base, secs = buf.data_ptr(), []
-                for j, (v, ln, fa) in enumerate(zip(views, lens, fasta)):
-                    rl = ln.ctypes.data_as(C.POINTER(C.c_uint32))
+                secs = []
+                for j, (v, fa) in enumerate(zip(views, fasta)):
                     d_seq = out_d.data_ptr() + int(at[j])
-                    secs.append(S.Section(base + ranges[j][0] + v.seq_off, d_seq, v.seq_size,
-                                          v.seq_ulen, 0, S.SEC_SEQ, rl, None, len(ln), None))
-                    if not fa:    # (the quality decoder reads the block's decoded bases)
-                        secs.append(S.Section(base + ranges[j][0] + v.qual_off, d_seq + v.seq_ulen,
-                                              v.qual_size, v.qual_ulen, 0, S.SEC_QUAL, rl, None,
-                                              len(ln), d_seq))
-                if any(r.status != 0 for r in S.decode(secs)):
-                    raise _lib.NativeError("section decoding failed: " + _lib.last_error())
+                    secs.append(win.section(j, S.SEC_SEQ, d_seq))
+                    if not fa:
+                        secs.append(win.section(j, S.SEC_QUAL, d_seq + v.seq_ulen, d_seq))
+                win.decode(secs)
             with _stage("stats"):
                 nw = sum(len(ln) for ln in lens)
                 if per_record:
@@ -2763,7 +2735,7 @@ def _stats(rd, cycles: int, mates: int, per_record: bool, device: str, window_by
                     rlen.extend(lens)
                     rqs.append(qs_d[:nw].cpu().numpy().view(np.uint64))
                     rgc.append(gc_d[:nw].cpu().numpy().view(np.uint32))
-            del buf, hv, out_d
+            del out_d
         with _stage("result"):
             flat = acc.read()
     with _stage("result"):
@@ -2792,11 +2764,5 @@ def stats(src, cycles: int = 1024, pairs: bool = False, per_record: bool = False
     in file order.  One process."""
     if not 1 <= cycles <= STATS_CYCLES_MAX:
         raise ValueError(f"stats: cycles {cycles} not in 1..{STATS_CYCLES_MAX}")
-    rd, close = _reader(src)
-    try:
-        res = _stats(rd, cycles, 2 if pairs else 1, per_record, device, window_bytes)
-    finally:
-        if close:
-            rd.close()
-    _trace_dump("stats")
-    return res
+    return _run(_reader(src), "stats", lambda rd: _stats(
+        rd, cycles, 2 if pairs else 1, per_record, device, window_bytes))
