@@ -12,6 +12,15 @@
 // one core each, so a candidate nobody reads is not free), then the trial
 // state machine is replayed on the host in block order, which gives exactly
 // the choices of a single-threaded (-t1) reference run.
+//
+// The try and the commit share their machinery: a Candidates holds the
+// requests of every coder family with one [section][method] table of where
+// each candidate lives, collect() is the one place that maps a method to its
+// family, size() / layout() read a candidate back, and run_candidates() codes
+// a Candidates: spread over the thread's helper contexts (the try), or with
+// only the fqz candidates on helpers (the commit's late encodes, and a try of
+// rANS candidates only).  Every helper thread is a host::Task started through
+// on_ctx(): joined, at the latest, when its scope unwinds.
 #include <atomic>
 #include <cstdio>
 #include <algorithm>
@@ -218,23 +227,129 @@ void staged_walk(const int32_t *sec_ids, int nsec, const uint32_t *avail,
 
 }  // namespace
 
-// Speculative candidates of the last fqz5_sections_try on this thread; they
-// live in the thread's GPU arena until fqz5_sections_commit.
-struct TrySession {
-    std::vector<CompressReq> reqs;
-    std::vector<std::vector<int>> req_of;
+using host::now_ms;
+using host::now_ns;
+using host::step_trace;
+
+// compress_with_methods' rANS call of method m (fqzcomp5.c:1992-2010)
+CompressReq rans_req(const fqz5_section &S, int m) {
+    CompressReq r;
+    r.d_in = S.in;
+    r.n = S.in_size;
+    r.order = method_order(m, S.fixed_len);
+    r.cap = compress_bound(r.n, r.order);
+    return r;
+}
+
+// An fqz or sequence-model candidate whose range chain was skipped (pruned, or
+// a bounds-only try): no bytes yet, its size as the interval [lb, ub].
+struct Bound {
+    bool skip = false;
+    uint64_t lb = 0, ub = 0;
+};
+
+// The candidates of a run of sections, by coder family, and where the
+// candidate of (section, method) lives.
+enum Family { FAM_NONE = 0, FAM_RANS, FAM_FQZ, FAM_SEQ, FAM_NAME };
+struct Candidates {
+    struct Slot { int fam = FAM_NONE, idx = -1; };
+    int nsec = 0;
+    std::vector<Slot> slots;                      // [nsec][FQZ5_M_LAST]
+    std::vector<CompressReq> rans;                // every rANS stream, once it ran LZP3's and the stripes' too
+    std::vector<CompressReq> stripes;             // RANSXN1 (stripe) candidates until join_stripes()
+    std::vector<int> stripe_sec;
+    std::vector<int> lzp_sec;                     // sections trying LZP3 until join_lzp()
     std::vector<FqzEncReq> fqz;                   // FQZ candidates
-    std::vector<uint64_t> fqz_lb;                 // pruned candidates: size lower bound (else 0)
-    std::vector<std::vector<int>> fqz_of;
     std::vector<SeqEncReq> seq;                   // sequence CM candidates
-    std::vector<uint64_t> seq_lb;                 // pruned candidates: size lower bound (else 0)
-    std::vector<uint64_t> fqz_ub, seq_ub;         // pruned candidates: size upper bound
-    std::vector<char> fqz_skip, seq_skip;         // range chain skipped: no bytes yet
-    std::vector<std::vector<int>> seq_of;
-    std::vector<uint32_t> upper;                  // the sizes matrix with upper bounds
+    std::vector<Bound> fqz_b, seq_b;              // one each
     std::deque<std::vector<uint32_t>> recs;       // their (rewritable) lengths / flags
-    std::vector<NameEnc> names;                   // name-section candidates (host bytes)
-    std::vector<std::vector<int>> name_of;
+    std::vector<int> name_sec, name_meth;         // name-section candidates
+    std::vector<NameEnc> names;                   // ... and their host bytes
+
+    explicit Candidates(int n = 0) : nsec(n), slots(size_t(std::max(n, 0)) * FQZ5_M_LAST) {}
+    Slot &at(int i, int m) { return slots[size_t(i) * FQZ5_M_LAST + size_t(m)]; }
+    Slot get(int i, int m) const {
+        return m > 0 && m < FQZ5_M_LAST ? slots[size_t(i) * FQZ5_M_LAST + size_t(m)] : Slot();
+    }
+    // the index of (i, m) in family fam's vector, -1 if it is no such candidate
+    int find(int i, int m, int fam) const {
+        const Slot s = get(i, m);
+        return s.fam == fam ? s.idx : -1;
+    }
+    void put_rans(int i, int m, CompressReq &&r) {
+        at(i, m) = {FAM_RANS, int(rans.size())};
+        rans.push_back(std::move(r));
+    }
+    void join_stripes() {                          // the stripe candidates join the batch
+        for (size_t k = 0; k < stripes.size(); k++) put_rans(stripe_sec[k], RANSXN1, std::move(stripes[k]));
+        stripes.clear();
+        stripe_sec.clear();
+    }
+    void join_lzp(std::vector<CompressReq> &&lzr) {   // the LZP3 streams (one per lzp_sec) join the batch
+        for (size_t k = 0; k < lzp_sec.size(); k++) put_rans(lzp_sec[k], LZP3, std::move(lzr[k]));
+        lzp_sec.clear();
+    }
+    // candidates whose cost grows with their work, or whose host work is worth
+    // a thread: those the try runs on helper contexts
+    bool wants_helpers() const {
+        return !fqz.empty() || !seq.empty() || !lzp_sec.empty() || !stripes.empty() || !name_sec.empty();
+    }
+    // the coder of (i, m) ran, whatever came of it: not a candidate whose
+    // range chain was skipped (those have no bytes)
+    bool coded(int i, int m) const {
+        const Slot s = get(i, m);
+        if (s.fam == FAM_FQZ) return !fqz_b[size_t(s.idx)].skip;
+        if (s.fam == FAM_SEQ) return !seq_b[size_t(s.idx)].skip;
+        return s.fam != FAM_NONE;
+    }
+    // The size of (i, m) as compress_with_methods sees it: UINT_MAX when not
+    // run, 0 when the codec returned NULL (out_len = *out_size = 0); a
+    // skipped candidate's lower bound, with its upper bound in *upper (else
+    // the size again).  *stale is the section's last good name size, for
+    // m = 0, 1, ... in turn: encode_names returns NULL without writing
+    // *out_size, so a failing name candidate is seen with the size the
+    // previous name candidate of this section wrote (fqzcomp5.c:2036-2044,
+    // :1433-1440); never strictly the best, but it enters the trial's totals
+    // (metrics_update) and can win the later blocks
+    uint32_t size(int i, int m, uint32_t *upper = nullptr, uint32_t *stale = nullptr) const {
+        auto clip = [](uint64_t v) { return uint32_t(std::min<uint64_t>(v, UINT32_MAX - 1)); };
+        const Slot s = get(i, m);
+        uint32_t sz = UINT32_MAX, up = 0;
+        if (s.fam == FAM_RANS) sz = rans[size_t(s.idx)].ok ? layout_size(rans[size_t(s.idx)].out) : 0;
+        // a name candidate's size is its whole section (encode_names' *out_size)
+        if (s.fam == FAM_NAME) {
+            const NameEnc &E = names[size_t(s.idx)];
+            sz = E.ok ? uint32_t(E.out.size()) : stale ? *stale : UINT32_MAX;
+            if (E.ok && stale) *stale = sz;
+        }
+        if (s.fam == FAM_FQZ || s.fam == FAM_SEQ) {
+            const Bound &b = s.fam == FAM_FQZ ? fqz_b[size_t(s.idx)] : seq_b[size_t(s.idx)];
+            const Layout *l = layout(i, m);
+            sz = l ? layout_size(*l) : b.lb ? clip(b.lb) : 0;
+            if (!l && b.ub) up = clip(b.ub);
+        }
+        if (upper) *upper = up ? up : sz;
+        return sz;
+    }
+    // the bytes of (i, m) if it was coded, else null (a name candidate's are in name())
+    const Layout *layout(int i, int m) const {
+        const Slot s = get(i, m);
+        if (s.fam == FAM_RANS && rans[size_t(s.idx)].ok) return &rans[size_t(s.idx)].out;
+        if (s.fam == FAM_FQZ && fqz[size_t(s.idx)].ok) return &fqz[size_t(s.idx)].out;
+        if (s.fam == FAM_SEQ && seq[size_t(s.idx)].ok) return &seq[size_t(s.idx)].out;
+        return nullptr;
+    }
+    const NameEnc *name(int i, int m) const {
+        const Slot s = get(i, m);
+        return s.fam == FAM_NAME ? &names[size_t(s.idx)] : nullptr;
+    }
+};
+
+// Speculative candidates of the last fqz5_sections_try on this thread; they
+// live in the thread's GPU arenas until fqz5_sections_commit.
+struct TrySession {
+    Candidates c;
+    std::vector<uint32_t> upper;                  // the sizes matrix with upper bounds
     bool open = false;
     bool aux = false;                             // candidates live in the helper contexts
     std::vector<int> predicted;                   // staged try: a follow section's provisional method (else -1)
@@ -339,27 +454,23 @@ bool staged_on() {
 }
 std::atomic<uint64_t> g_chains_host{0}, g_chains_gpu{0};   // fqz5_decode_chain_counts
 
-// Which requests of one family of work candidates (fqz methods FQZ0..FQZ4 on
-// quality sections, or the sequence models SEQ10..SEQ14B) to skip, from the
-// exact sizes of the earlier (rANS) methods and the family's lower bounds.
-// of[i][m]: the request index of method m in section i (-1 if none); lb(k):
-// request k's size lower bound (0 if unknown).
+// Which candidates of one family of work candidates (fam: fqz methods
+// FQZ0..FQZ4 on quality sections, or the sequence models SEQ10..SEQ14B) to
+// skip, from the exact sizes of the earlier (rANS) methods and the family's
+// lower bounds: sets bounds[k].skip.  lb(k): candidate k's size lower bound
+// (0 if unknown).
 template <class LB>
-std::vector<char> prune_plan(const std::vector<CompressReq> &reqs,
-                             const std::vector<std::vector<int>> &of, int mlo, int mhi,
-                             size_t nreq, LB lb) {
-    std::vector<char> skip(nreq, 0);
-    const int nsec = int(of.size());
+void prune_plan(const Candidates &C, int fam, int mlo, int mhi, std::vector<Bound> &bounds, LB lb) {
     std::vector<int> F;                                 // sections trying the family
-    for (int i = 0; i < nsec; i++)
+    for (int i = 0; i < C.nsec; i++)
         for (int m = mlo; m <= mhi; m++)
-            if (of[i][m] >= 0) { F.push_back(i); break; }
+            if (C.find(i, m, fam) >= 0) { F.push_back(i); break; }
     // one whole trial window: every method's usize is then the same, and the
     // window's pick (min (csize + 1) / usize) compares plain sums
-    if (F.size() != size_t(FQZ5_METRICS_TRIAL)) return skip;
+    if (F.size() != size_t(FQZ5_METRICS_TRIAL)) return;
     auto rsize = [&](int i, int m) -> int64_t {          // exact rANS size, -1 if none
-        const int ri = t_sess.req_of[i][m];
-        return ri >= 0 && reqs[size_t(ri)].ok ? int64_t(layout_size(reqs[size_t(ri)].out)) : -1;
+        const Layout *l = C.find(i, m, FAM_RANS) >= 0 ? C.layout(i, m) : nullptr;
+        return l ? int64_t(layout_size(*l)) : -1;
     };
     std::vector<int64_t> best(F.size(), -1);            // per section: min earlier size
     for (size_t k = 0; k < F.size(); k++)
@@ -382,7 +493,7 @@ std::vector<char> prune_plan(const std::vector<CompressReq> &reqs,
         bool ok = true;
         int64_t lbsum = 0;
         for (size_t k = 0; k < F.size() && ok; k++) {
-            const int fi = of[F[k]][m];
+            const int fi = C.find(F[k], m, fam);
             if (fi < 0) { ok = false; break; }            // must be tried in the whole window
             const int64_t b = int64_t(lb(size_t(fi)));
             ok = b > 0 && best[k] >= 0 && b >= best[k];
@@ -390,17 +501,54 @@ std::vector<char> prune_plan(const std::vector<CompressReq> &reqs,
         }
         if (!ok || !(best_sum >= 0 && lbsum >= best_sum)) continue;
         for (int i : F)
-            if (of[i][m] >= 0) skip[size_t(of[i][m])] = 1;
+            if (C.find(i, m, fam) >= 0) bounds[size_t(C.find(i, m, fam))].skip = true;
     }
-    return skip;
 }
 
-// LZP3 candidates of sections `which`: their lzp output (device, this
-// context's arena) joins `reqs` as an order-5 rANS request; of[i][LZP3]
-// gets its index.
-void add_lzp3(GpuCtx &g, const fqz5_section *secs, const std::vector<int> &which,
-              std::vector<CompressReq> &reqs, std::vector<std::vector<int>> &of) {
-    if (which.empty()) return;
+// Adds the candidates of masks[i] for every section: the one place that maps
+// a method to its coder family.  A method that does not fit its section adds
+// nothing (fqz5_sections_try refuses such masks first; fqz5_sections_commit
+// leaves the section without bytes).  The stripe and LZP3 candidates get
+// their place in the table when they join the batch.
+void collect(Candidates &C, const fqz5_section *secs, const uint32_t *masks) {
+    for (int i = 0; i < C.nsec; i++) {
+        const fqz5_section &S = secs[i];
+        for (int m = 1; m < FQZ5_M_LAST; m++) {
+            if (!(masks[i] & (1u << m))) continue;
+            if (is_name_method(m) != (S.sec == FQZ5_SEC_NAME)) continue;
+            if (is_name_method(m)) {
+                C.at(i, m) = {FAM_NAME, int(C.name_sec.size())};
+                C.name_sec.push_back(i);
+                C.name_meth.push_back(m);
+            } else if (is_fqz(m)) {
+                if (S.sec != FQZ5_SEC_QUAL || !S.rec_len) continue;
+                C.at(i, m) = {FAM_FQZ, int(C.fqz.size())};
+                C.fqz.push_back(fqz_req(S, m, C.recs));
+                C.fqz_b.emplace_back();
+            } else if (is_seqcm(m)) {
+                if (S.sec != FQZ5_SEC_SEQ || !S.rec_len) continue;
+                C.at(i, m) = {FAM_SEQ, int(C.seq.size())};
+                C.seq.push_back(seq_req(S, m));
+                C.seq_b.emplace_back();
+            } else if (m == LZP3) {                            // after the lzp pass
+                C.lzp_sec.push_back(i);
+            } else if (m == RANSXN1) {                         // thousands of short stripe chains
+                if (!S.fixed_len) continue;                    // out = NULL (:2004-2007)
+                C.stripe_sec.push_back(i);
+                C.stripes.push_back(rans_req(S, m));
+            } else if (RANS_MASK & (1u << m)) {
+                C.put_rans(i, m, rans_req(S, m));
+            }
+        }
+    }
+}
+
+// The LZP3 candidates of sections `which` (fqzcomp5.c:2013-2021): the lzp pass
+// on context g; its output (device, g's arena) as one order-5 rANS request
+// each.
+std::vector<CompressReq> lzp_reqs(GpuCtx &g, const fqz5_section *secs, const std::vector<int> &which) {
+    std::vector<CompressReq> out(which.size());
+    if (which.empty()) return out;
     std::vector<LzpEncReq> lz(which.size());
     for (size_t k = 0; k < which.size(); k++) {
         lz[k].d_in = secs[which[k]].in;
@@ -408,14 +556,206 @@ void add_lzp3(GpuCtx &g, const fqz5_section *secs, const std::vector<int> &which
     }
     lzp_encode_batch(g, lz);
     for (size_t k = 0; k < which.size(); k++) {
-        CompressReq r;
+        CompressReq &r = out[k];
         r.d_in = lz[k].d_out;
         r.n = lz[k].out_len;
         r.order = 5;
         r.cap = compress_bound(r.n, r.order);
-        of[size_t(which[k])][LZP3] = int(reqs.size());
-        reqs.push_back(std::move(r));
     }
+    return out;
+}
+
+// fn() on a thread of its own for context c (an empty fn: none).  The caller
+// takes c: gpu_aux() gives the calling thread's contexts.  A new thread
+// starts on device 0, and c's arena may grow (hipMalloc on the current
+// device), so c's device comes first.  Joined by join() or by leaving the
+// scope, so before any reset() of c.
+host::Task on_ctx(GpuCtx &c, const char *who, double t0, std::function<void()> fn) {
+    if (!fn) return host::Task();
+    return host::Task([&c, who, t0, fn = std::move(fn)] {
+        FQZ5_HIP(hipSetDevice(c.device));
+        fn();
+        if (step_trace())
+            std::fprintf(stderr, "%s: helper context %p done at %.1f ms\n", who,
+                         static_cast<void *>(&c), now_ms() - t0);
+    });
+}
+
+// Requests dealt round-robin into ng groups (one helper context each), and
+// their work back in request order.
+template <class R>
+std::vector<std::vector<R>> deal(std::vector<R> &v, size_t ng) {
+    std::vector<std::vector<R>> grp(ng);
+    for (size_t k = 0; k < v.size(); k++) grp[k % ng].push_back(std::move(v[k]));
+    return grp;
+}
+template <class R>
+void deal_back(std::vector<R> &v, std::vector<std::vector<R>> &grp) {
+    for (size_t k = 0; k < v.size(); k++) v[k] = std::move(grp[k % grp.size()][k / grp.size()]);
+}
+
+// A batch of rANS requests on g.  With a plain_ctx, the plain O0/O1 requests
+// (RANS0/RANS1: the longest chains, one step per 4 input bytes) of 2^20 B and
+// more need no PACK / RLE pass: they run as a batch of their own on that
+// helper context, so that their chains start while this thread packs and
+// run-length codes the others' inputs (the packed chains are half as long or
+// less); unless the batch holds one kind only.
+void rans_batch(GpuCtx &g, GpuCtx *plain_ctx, std::vector<CompressReq> &reqs, const char *who,
+                double t0) {
+    if (reqs.empty()) return;
+    std::vector<char> is_plain(reqs.size(), 0);
+    size_t np = 0;
+    for (size_t k = 0; k < reqs.size(); k++)
+        np += is_plain[k] = plain_ctx && (reqs[k].order & ~1) == 0 && reqs[k].n >= (1u << 20);
+    if (np == 0 || np == reqs.size()) {
+        compress_batch(g, reqs);
+        return;
+    }
+    std::vector<CompressReq> plain, rest;
+    for (size_t k = 0; k < reqs.size(); k++) (is_plain[k] ? plain : rest).push_back(std::move(reqs[k]));
+    plain_ctx->prof.on = g.prof.on;
+    host::Task tp = on_ctx(*plain_ctx, who, t0, [&] { compress_batch(*plain_ctx, plain); });
+    compress_batch(g, rest);
+    const double tc = step_trace() ? now_ms() : 0;
+    tp.join();
+    if (step_trace())
+        std::fprintf(stderr, "%s: %zu plain rANS candidates on a helper, done %.1f ms after the "
+                     "others\n", who, plain.size(), now_ms() - tc);
+    size_t qp = 0, qr = 0;                               // back in request order
+    for (size_t k = 0; k < reqs.size(); k++) reqs[k] = std::move(is_plain[k] ? plain[qp++] : rest[qr++]);
+    g.prof.enc_ms += plain_ctx->prof.enc_ms;
+    g.prof.enc_launches += plain_ctx->prof.enc_launches;
+    g.prof.enc_bytes += plain_ctx->prof.enc_bytes;
+    plain_ctx->prof = KernelProfile();
+}
+
+// What fqz5_sections_try adds to run_candidates.
+struct RunHooks {
+    // the second stage of a staged try: once every rANS batch (the stripes'
+    // too) has sizes, while the other helpers are still at work; plain_ctx as
+    // for rans_batch
+    std::function<void(GpuCtx *plain_ctx)> after_rans;
+    // trial pruning / a bounds-only try: sets Bound::skip of the fqz and
+    // sequence-model candidates, after their model passes, before their chains
+    std::function<void()> before_chains;
+};
+
+// Codes every candidate of C.  spread (fqz5_sections_try, when a candidate
+// wants a helper): the candidates whose cost grows with their work (trial
+// blocks only) run on the thread's helper contexts from helper threads,
+// beside the rANS candidates on g (a few long chains that leave most of the
+// GPU idle): LZP3 (the lzp pass, then rANS order 5 of its output), the fqz
+// and the sequence-model model passes, the stripes, the names.  Then
+// hk.before_chains marks the fqz / sequence-model candidates to skip, and the
+// others' range chains run.  Otherwise (fqz5_sections_commit's late encodes,
+// a try of rANS candidates only) everything runs on g but the fqz candidates.
+// Returns whether helper contexts hold bytes of C now.
+bool run_candidates(Candidates &C, const fqz5_section *secs, GpuCtx &g, bool spread,
+                    const RunHooks &hk, const char *who, double t0) {
+    // fn(context k) on a thread of its own, if `need`
+    auto helper = [&](int k, bool need, auto fn) {
+        if (!need) return host::Task();
+        GpuCtx &c = gpu_aux(k);
+        return on_ctx(c, who, t0, [&c, fn] { fn(c); });
+    };
+    if (!spread || !C.wants_helpers()) {
+        // The late fqz encodes (-5 Illumina: every block's quality section;
+        // their range chains, ~1.2 s for a 100 MB block, are the commit's
+        // long pole) start first, in groups on the helper contexts (the
+        // sequence models' ones, idle now), so that each group's chains start
+        // when its own model pass is done, and the other late encodes run
+        // beside them on this thread.
+        std::vector<std::vector<FqzEncReq>> fgrp = deal(C.fqz, std::min(C.fqz.size(), size_t(AUX_NSEQ)));
+        std::vector<host::Task> tf;
+        for (size_t q = 0; q < fgrp.size(); q++)
+            tf.push_back(helper(int(AUX_SEQ0 + q), true,
+                                [&grp = fgrp[q]](GpuCtx &c) { fqz_encode_batch(c, grp); }));
+        C.join_lzp(lzp_reqs(g, secs, C.lzp_sec));
+        C.join_stripes();
+        rans_batch(g, nullptr, C.rans, who, t0);
+        if (hk.after_rans) hk.after_rans(nullptr);
+        if (!C.seq.empty()) seq_encode_batch(g, C.seq);
+        encode_name_jobs(g, secs, C.name_sec, C.name_meth, C.names);
+        for (host::Task &t : tf) t.join();
+        if (!fgrp.empty()) deal_back(C.fqz, fgrp);
+        return !fgrp.empty();
+    }
+    // sequence-model candidates: one helper context each (their passes are
+    // latency-bound and overlap well), up to AUX_NSEQ (each runs one block at
+    // a time with ~120 B of device memory per base while it prepares: as many
+    // side by side as fit a quarter of HBM; -9's 1 GB blocks take them one
+    // after another)
+    size_t nsq = std::min<size_t>(C.seq.size(), size_t(AUX_NSEQ));
+    if (nsq) {
+        uint64_t mx = 1;
+        for (const SeqEncReq &q : C.seq) mx = std::max<uint64_t>(mx, q.n);
+        size_t fr = 0, tot = 0;
+        if (hipMemGetInfo(&fr, &tot) != hipSuccess || !tot) tot = size_t(64) << 30;
+        const uint64_t fit = (uint64_t(tot) / 4) / (120 * mx);
+        nsq = std::max<size_t>(1, std::min<size_t>(nsq, size_t(fit)));
+    }
+    std::vector<std::vector<SeqEncReq>> sqg = deal(C.seq, nsq);
+    std::vector<CompressReq> lzr;
+    std::vector<char> skip_f(C.fqz.size(), 0), skip_s(C.seq.size(), 0);
+    GpuCtx &gp = gpu_aux(AUX_PLAIN);
+    host::Task t_lzp = helper(AUX_LZP, !C.lzp_sec.empty(), [&](GpuCtx &c) {
+        lzr = lzp_reqs(c, secs, C.lzp_sec);
+        compress_batch(c, lzr);
+    });
+    host::Task t_fqz = helper(AUX_FQZ, !C.fqz.empty(), [&](GpuCtx &c) { fqz_encode_prepare(c, C.fqz); });
+    // The RANSXN1 candidates (150 stripes x 4 orders per quality section:
+    // most of a batch's jobs, and most of its host work on tables) run as
+    // their own batch on a helper context, so that their host work overlaps
+    // the long chains of the other rANS candidates on the GPU.
+    host::Task t_stripes = helper(AUX_STRIPES, !C.stripes.empty(),
+                                  [&](GpuCtx &c) { compress_batch(c, C.stripes); });
+    // the name candidates: host tokenising, then their own batches
+    host::Task t_names = helper(AUX_NAMES, !C.name_sec.empty(), [&](GpuCtx &c) {
+        encode_name_jobs(c, secs, C.name_sec, C.name_meth, C.names);
+    });
+    std::vector<host::Task> t_seq;
+    for (size_t k = 0; k < nsq; k++)
+        t_seq.push_back(helper(int(AUX_SEQ0 + k), true,
+                               [&grp = sqg[k]](GpuCtx &c) { seq_encode_prepare(c, grp); }));
+    rans_batch(g, &gp, C.rans, who, t0);
+    // the three rANS batches first (the stripes' too): their sizes decide the
+    // second stage, which runs beside the other helpers
+    t_stripes.join();
+    C.join_stripes();
+    if (hk.after_rans) hk.after_rans(&gp);
+    const double tc = step_trace() ? now_ms() : 0;
+    t_lzp.join();
+    t_fqz.join();
+    for (host::Task &t : t_seq) t.join();
+    t_names.join();
+    if (step_trace())
+        std::fprintf(stderr, "%s: rANS candidates %.1f ms, helpers waited %.1f ms more\n", who,
+                     tc - t0, now_ms() - tc);
+    if (nsq) deal_back(C.seq, sqg);
+    C.join_lzp(std::move(lzr));
+    if (hk.before_chains) hk.before_chains();
+    for (size_t k = 0; k < C.fqz.size(); k++) skip_f[k] = C.fqz_b[k].skip;
+    for (size_t k = 0; k < C.seq.size(); k++) skip_s[k] = C.seq_b[k].skip;
+    // the fqz chains on their helper beside the sequence models' on this thread
+    host::Task t_chains = helper(AUX_FQZ, !C.fqz.empty(),
+                                 [&](GpuCtx &c) { fqz_encode_finish(c, C.fqz, &skip_f); });
+    if (!C.seq.empty()) {
+        GpuCtx &gb = gpu_aux(AUX_SEQ0);
+        FQZ5_HIP(hipSetDevice(gb.device));
+        seq_encode_finish(gb, C.seq, &skip_s);
+    }
+    t_chains.join();
+    for (size_t k = 0; k < C.fqz.size(); k++)
+        if (skip_f[k]) {
+            C.fqz_b[k].lb = fqz_size_lower_bound(C.fqz[k]);
+            C.fqz_b[k].ub = fqz_size_upper_bound(C.fqz[k]);
+        }
+    for (size_t k = 0; k < C.seq.size(); k++)
+        if (skip_s[k]) {
+            C.seq_b[k].lb = seq_size_lower_bound(C.seq[k]);
+            C.seq_b[k].ub = seq_size_upper_bound(C.seq[k]);
+        }
+    return true;
 }
 
 }  // namespace fqz5
@@ -498,10 +838,6 @@ void fqz5_staged_decisions(uint64_t out[FQZ5_SEC_LAST]) {
     for (int k = 0; k < FQZ5_SEC_LAST; k++) out[k] = g_staged_dec[k].load();
 }
 
-using host::now_ms;
-using host::now_ns;
-using host::step_trace;
-
 }  // extern "C"
 
 // fqz5_sections_try, and with `avail` and `st` (and staged tries on)
@@ -557,80 +893,19 @@ static int sections_try_impl(const fqz5_section *secs, int nsec, const uint32_t 
             if ((masks[i] & FQZ_MASK) && (secs[i].sec != FQZ5_SEC_QUAL || !secs[i].rec_len))
                 throw GpuError("fqz5_sections_try: FQZ methods need a quality section with records");
         }
-        std::vector<CompressReq> &reqs = t_sess.reqs;
-        t_sess.req_of.assign(nsec, std::vector<int>(FQZ5_M_LAST, -1));
-        t_sess.fqz_of.assign(nsec, std::vector<int>(FQZ5_M_LAST, -1));
-        t_sess.seq_of.assign(nsec, std::vector<int>(FQZ5_M_LAST, -1));
-        t_sess.name_of.assign(nsec, std::vector<int>(FQZ5_M_LAST, -1));
-        std::vector<int> name_sec, name_meth;             // name candidates
-        std::vector<int> lzp_sec;                         // sections trying LZP3
-        std::vector<CompressReq> sreq;                    // RANSXN1 (stripe) candidates
-        std::vector<int> sreq_sec;
-        for (int i = 0; i < nsec; i++) {
-            const fqz5_section &S = secs[i];
-            for (int m = 1; m < FQZ5_M_LAST; m++) {
-                if (!(masks[i] & (1u << m))) continue;
-                if (is_fqz(m)) {
-                    t_sess.fqz_of[i][m] = int(t_sess.fqz.size());
-                    t_sess.fqz.push_back(fqz_req(S, m, t_sess.recs));
-                    continue;
-                }
-                if (is_seqcm(m)) {
-                    t_sess.seq_of[i][m] = int(t_sess.seq.size());
-                    t_sess.seq.push_back(seq_req(S, m));
-                    continue;
-                }
-                if (is_name_method(m)) {
-                    t_sess.name_of[i][m] = int(name_sec.size());
-                    name_sec.push_back(i);
-                    name_meth.push_back(m);
-                    continue;
-                }
-                if (m == RANSXN1 && !S.fixed_len) continue;   // out = NULL (:2004-2007)
-                if (m == LZP3) {                               // after the lzp pass, below
-                    lzp_sec.push_back(i);
-                    continue;
-                }
-                CompressReq r;
-                r.d_in = S.in;
-                r.n = S.in_size;
-                r.order = method_order(m, S.fixed_len);
-                r.cap = compress_bound(r.n, r.order);
-                if (m == RANSXN1) {          // thousands of short stripe chains
-                    sreq_sec.push_back(i);
-                    sreq.push_back(std::move(r));
-                    continue;
-                }
-                t_sess.req_of[i][m] = int(reqs.size());
-                reqs.push_back(std::move(r));
-            }
-        }
-        // The candidates whose cost grows with their work (trial blocks only)
-        // run on the thread's helper contexts from helper threads, beside the
-        // rANS candidates (a few long chains that leave most of the GPU
-        // idle): LZP3 (the lzp pass, then rANS order 5 of its output,
-        // fqzcomp5.c:2013-2021), the fqz and the sequence-model model passes.
-        // Then the fqz / sequence-model candidates that provably lose the
-        // trial are pruned, and the others' range chains run.
-        static const bool no_aux = std::getenv("FQZ5_NO_AUX") != nullptr;
-        std::vector<FqzEncReq> &fq = t_sess.fqz;
-        std::vector<SeqEncReq> &sq = t_sess.seq;
-        auto join_stripes = [&] {          // the stripe candidates join the batch
-            for (size_t k = 0; k < sreq.size(); k++) {
-                t_sess.req_of[size_t(sreq_sec[k])][RANSXN1] = int(reqs.size());
-                reqs.push_back(std::move(sreq[k]));
-            }
-            sreq.clear();
-        };
+        // (t_sess is thread_local: the helper threads get the caller's
+        // candidates by reference)
+        Candidates &C = t_sess.c = Candidates(nsec);
+        collect(C, secs, masks);
         if (staged)
-            g_staged_n[0] += reqs.size() + sreq.size() + lzp_sec.size() + fq.size() + sq.size();
+            g_staged_n[0] += C.rans.size() + C.stripes.size() + C.lzp_sec.size() + C.fqz.size() + C.seq.size();
+        RunHooks hk;
         // The second stage: each decision's pick over the sizes its window's
         // rANS candidates have now (the first smallest (csize + 1) / usize,
         // as metrics_method picks), and the follow sections coded with it; the
         // plain chains on `plain_ctx` beside the others when there is one.
-        auto stage2 = [&](GpuCtx *plain_ctx) {
-            std::vector<CompressReq> s2;
-            std::vector<int> s2_sec, s2_m;
+        if (staged) hk.after_rans = [&](GpuCtx *plain_ctx) {
+            std::vector<uint32_t> pick(size_t(nsec), 0);     // the follow sections' one-bit masks
             for (const Decision &d : decs) {
                 fqz5_section_stats s = st->sec[d.kind];
                 if (d.fresh) {
@@ -641,10 +916,8 @@ static int sections_try_impl(const fqz5_section *secs, int nsec, const uint32_t 
                 for (int i : d.rows)
                     for (int m = 1; m < FQZ5_M_LAST; m++) {
                         if (!(masks_in[i] & RANS_MASK & (1u << m))) continue;
-                        const int ri = t_sess.req_of[size_t(i)][m];
                         s.usize[m] += secs[i].in_size;
-                        s.csize[m] += ri < 0 ? UINT32_MAX
-                                      : reqs[size_t(ri)].ok ? layout_size(reqs[size_t(ri)].out) : 0;
+                        s.csize[m] += C.size(i, m);
                     }
                 const int w = pick_method(s, RANS_MASK);
                 g_staged_dec[d.kind]++;
@@ -652,292 +925,55 @@ static int sections_try_impl(const fqz5_section *secs, int nsec, const uint32_t 
                     std::fprintf(stderr, "sections_try: staged: kind %d decided at %.1f ms: method %d "
                                  "for %zu sections\n", d.kind, now_ms() - t0, w, d.follow.size());
                 if (!w) continue;
-                for (int i : d.follow) {
-                    const fqz5_section &S = secs[i];
-                    if (!(masks_in[i] & (1u << w)) || (w == RANSXN1 && !S.fixed_len)) continue;
-                    CompressReq r;
-                    r.d_in = S.in;
-                    r.n = S.in_size;
-                    r.order = method_order(w, S.fixed_len);
-                    r.cap = compress_bound(r.n, r.order);
-                    s2.push_back(std::move(r));
-                    s2_sec.push_back(i);
-                    s2_m.push_back(w);
-                }
+                for (int i : d.follow) pick[size_t(i)] = masks_in[i] & (1u << w);
             }
-            if (s2.empty()) return;
-            std::vector<CompressReq> pl, rest;
-            std::vector<char> is_pl(s2.size(), 0);
-            for (size_t k = 0; k < s2.size(); k++)
-                is_pl[k] = plain_ctx && (s2[k].order & ~1) == 0 && s2[k].n >= (1u << 20);
-            for (size_t k = 0; k < s2.size(); k++) (is_pl[k] ? pl : rest).push_back(std::move(s2[k]));
-            if (pl.empty() || rest.empty()) {
-                compress_batch(g, pl.empty() ? rest : pl);
-            } else {
-                std::exception_ptr e2;
-                plain_ctx->prof.on = g.prof.on;
-                std::thread t2([&] {
-                    try {
-                        FQZ5_HIP(hipSetDevice(plain_ctx->device));
-                        compress_batch(*plain_ctx, pl);
-                    } catch (...) {
-                        e2 = std::current_exception();
-                    }
-                });
-                try {
-                    compress_batch(g, rest);
-                } catch (...) {
-                    t2.join();
-                    throw;
-                }
-                t2.join();
-                if (e2) std::rethrow_exception(e2);
-                g.prof.enc_ms += plain_ctx->prof.enc_ms;
-                g.prof.enc_launches += plain_ctx->prof.enc_launches;
-                g.prof.enc_bytes += plain_ctx->prof.enc_bytes;
-                plain_ctx->prof = KernelProfile();
+            Candidates s2(nsec);
+            collect(s2, secs, pick.data());
+            s2.join_stripes();
+            if (s2.rans.empty()) return;
+            rans_batch(g, plain_ctx, s2.rans, "sections_try", t0);
+            const size_t n2 = s2.rans.size();
+            for (int i = 0; i < nsec; i++) {
+                const int m = pick[size_t(i)] ? __builtin_ctz(pick[size_t(i)]) : 0;
+                const int k = s2.find(i, m, FAM_RANS);
+                if (k < 0) continue;
+                C.put_rans(i, m, std::move(s2.rans[size_t(k)]));
+                t_sess.predicted[size_t(i)] = m;
             }
-            size_t qp = 0, qr = 0;
-            for (size_t k = 0; k < s2_sec.size(); k++) {
-                t_sess.req_of[size_t(s2_sec[k])][s2_m[k]] = int(reqs.size());
-                t_sess.predicted[size_t(s2_sec[k])] = s2_m[k];
-                reqs.push_back(std::move(is_pl[k] ? pl[qp++] : rest[qr++]));
-            }
-            g_staged_n[1] += s2_sec.size();
-            g_staged_n[3] -= s2_sec.size();
+            g_staged_n[1] += n2;
+            g_staged_n[3] -= n2;
             if (step_trace())
                 std::fprintf(stderr, "sections_try: staged: stage 2 (%zu sections) done at %.1f ms\n",
-                             s2_sec.size(), now_ms() - t0);
+                             n2, now_ms() - t0);
         };
-        if ((!fq.empty() || !sq.empty() || !lzp_sec.empty() || !sreq.empty() || !name_sec.empty()) &&
-            !no_aux) {
-            t_sess.aux = true;
-            GpuCtx &ga = gpu_aux(0), &gb = gpu_aux(2), &gc = gpu_aux(1);
-            // sequence-model candidates: one helper context each (their
-            // passes are latency-bound and overlap well), up to AUX_NSEQ
-            // (each runs one block at a time with ~120 B of device memory per
-            // base while it prepares: as many side by side as fit a quarter of
-            // HBM; -9's 1 GB blocks take them one after another)
-            size_t nsq = std::min<size_t>(sq.size(), size_t(AUX_NSEQ));
-            {
-                uint64_t mx = 1;
-                for (const SeqEncReq &q : sq) mx = std::max<uint64_t>(mx, q.n);
-                size_t fr = 0, tot = 0;
-                if (hipMemGetInfo(&fr, &tot) != hipSuccess || !tot) tot = size_t(64) << 30;
-                const uint64_t fit = (uint64_t(tot) / 4) / (120 * mx);
-                nsq = std::max<size_t>(1, std::min<size_t>(nsq, size_t(fit)));
-            }
-            std::vector<std::vector<SeqEncReq>> sqg(nsq);
-            for (size_t k = 0; k < sq.size(); k++) sqg[k % std::max<size_t>(nsq, 1)].push_back(sq[k]);
-            std::vector<CompressReq> lzr;
-            std::vector<std::vector<int>> lzr_of(size_t(nsec), std::vector<int>(FQZ5_M_LAST, -1));
-            std::vector<std::exception_ptr> err(2 + nsq);
-            auto on = [t0](GpuCtx &c, std::exception_ptr &e, auto &&fn) {
-                return std::thread([&c, &e, fn, t0] {
-                    try {
-                        FQZ5_HIP(hipSetDevice(c.device));
-                        fn();
-                        if (step_trace())
-                            std::fprintf(stderr, "sections_try: helper context %p done at %.1f ms\n",
-                                         static_cast<void *>(&c), now_ms() - t0);
-                    } catch (...) {
-                        e = std::current_exception();
-                    }
-                });
-            };
-            std::vector<std::thread> th;
-            th.push_back(on(gc, err[0], [&] {
-                add_lzp3(gc, secs, lzp_sec, lzr, lzr_of);
-                if (!lzr.empty()) compress_batch(gc, lzr);
-            }));
-            th.push_back(on(ga, err[1], [&] { if (!fq.empty()) fqz_encode_prepare(ga, fq); }));
-            // The RANSXN1 candidates (150 stripes x 4 orders per quality
-            // section: most of a batch's jobs, and most of its host work on
-            // tables) run as their own batch on a helper context, so that
-            // their host work overlaps the long chains of the other rANS
-            // candidates on the GPU.
-            GpuCtx &gs = gpu_aux(AUX_STRIPES);
-            std::exception_ptr serr;
-            std::thread ts = on(gs, serr, [&] { if (!sreq.empty()) compress_batch(gs, sreq); });
-            // the name candidates: host tokenising, then their own batches
-            // (t_sess is thread_local: the helper thread gets the caller's
-            // vector by reference)
-            GpuCtx &gn = gpu_aux(AUX_NAMES);
-            std::exception_ptr nerr;
-            std::vector<NameEnc> &nres = t_sess.names;
-            std::thread tn = on(gn, nerr, [&] {
-                encode_name_jobs(gn, secs, name_sec, name_meth, nres);
-            });
-            for (size_t k = 0; k < nsq; k++) {
-                GpuCtx &gk = gpu_aux(int(AUX_SEQ0 + k));
-                std::vector<SeqEncReq> &grp = sqg[k];
-                th.push_back(on(gk, err[2 + k], [&gk, &grp] { seq_encode_prepare(gk, grp); }));
-            }
-            // The plain O0/O1 candidates (RANS0/RANS1: the longest chains,
-            // one step per 4 input bytes) need no PACK / RLE pass: they run
-            // as a batch of their own on a helper context, so that their
-            // chains start while this thread packs and run-length codes the
-            // others' inputs (the packed chains are half as long or less).
-            std::vector<size_t> plain_at;
-            std::vector<char> is_plain(reqs.size(), 0);
-            std::vector<CompressReq> plain, rest;
-            for (size_t k = 0; k < reqs.size(); k++)
-                if ((reqs[k].order & ~1) == 0 && reqs[k].n >= (1u << 20)) plain_at.push_back(k);
-            if (plain_at.size() == reqs.size()) plain_at.clear();
-            for (size_t k : plain_at) is_plain[k] = 1;
-            if (!plain_at.empty())
-                for (size_t k = 0; k < reqs.size(); k++)
-                    (is_plain[k] ? plain : rest).push_back(std::move(reqs[k]));
-            GpuCtx &gp = gpu_aux(AUX_PLAIN);
-            gp.prof.on = g.prof.on;
-            std::exception_ptr perr;
-            std::thread tp = on(gp, perr, [&] { if (!plain.empty()) compress_batch(gp, plain); });
-            double tc = 0, tpl = 0;
-            try {
-                compress_batch(g, plain_at.empty() ? reqs : rest);
-                if (!plain_at.empty()) {             // back in request order
-                    size_t q = 0;
-                    for (size_t k = 0; k < reqs.size(); k++)
-                        if (!is_plain[k]) reqs[k] = std::move(rest[q++]);
-                }
-                tc = step_trace() ? now_ms() : 0;
-                tp.join();
-                tpl = step_trace() ? now_ms() : 0;
-                // the three rANS batches first (the stripes' too): their sizes
-                // decide the second stage, which runs beside the other helpers
-                ts.join();
-                if (perr) std::rethrow_exception(perr);
-                if (serr) std::rethrow_exception(serr);
-                for (size_t q = 0; q < plain_at.size(); q++) reqs[plain_at[q]] = std::move(plain[q]);
-                g.prof.enc_ms += gp.prof.enc_ms;
-                g.prof.enc_launches += gp.prof.enc_launches;
-                g.prof.enc_bytes += gp.prof.enc_bytes;
-                gp.prof = KernelProfile();
-                if (step_trace() && !plain_at.empty())
-                    std::fprintf(stderr, "sections_try: %zu plain rANS candidates on a helper, "
-                                 "done %.1f ms after the others\n", plain_at.size(), tpl - tc);
-                join_stripes();
-                if (staged) stage2(&gp);
-                tc = step_trace() ? now_ms() : 0;
-            } catch (...) {
-                if (tp.joinable()) tp.join();
-                if (ts.joinable()) ts.join();
-                for (auto &t : th) t.join();
-                tn.join();
-                throw;
-            }
-            for (auto &t : th) t.join();
-            tn.join();
-            if (nerr) std::rethrow_exception(nerr);
-            if (step_trace())
-                std::fprintf(stderr, "sections_try: rANS candidates %.1f ms, helpers waited "
-                             "%.1f ms more\n", tc - t0, now_ms() - tc);
-            for (auto &e : err)
-                if (e) std::rethrow_exception(e);
-            for (size_t k = 0; k < sq.size(); k++)          // their work back in request order
-                sq[k] = std::move(sqg[k % std::max<size_t>(nsq, 1)][k / std::max<size_t>(nsq, 1)]);
-            for (int i : lzp_sec) {                     // the LZP3 streams join the batch
-                t_sess.req_of[size_t(i)][LZP3] = int(reqs.size());
-                reqs.push_back(std::move(lzr[size_t(lzr_of[size_t(i)][LZP3])]));
-            }
-            std::vector<char> skip_f(fq.size(), 0), skip_s(sq.size(), 0);
+        hk.before_chains = [&C] {
             if (g_bounds.load()) {
-                for (size_t k = 0; k < fq.size(); k++) skip_f[k] = fqz_size_lower_bound(fq[k]) > 0;
-                for (size_t k = 0; k < sq.size(); k++) skip_s[k] = seq_size_upper_bound(sq[k]) > 0;
+                for (size_t k = 0; k < C.fqz.size(); k++) C.fqz_b[k].skip = fqz_size_lower_bound(C.fqz[k]) > 0;
+                for (size_t k = 0; k < C.seq.size(); k++) C.seq_b[k].skip = seq_size_upper_bound(C.seq[k]) > 0;
             } else if (g_prune.load()) {
-                skip_f = prune_plan(reqs, t_sess.fqz_of, FQZ0, FQZ4, fq.size(),
-                                    [&](size_t k) { return fqz_size_lower_bound(fq[k]); });
-                skip_s = prune_plan(reqs, t_sess.seq_of, SEQ10, SEQ14B, sq.size(),
-                                    [&](size_t k) { return seq_size_lower_bound(sq[k]); });
+                prune_plan(C, FAM_FQZ, FQZ0, FQZ4, C.fqz_b,
+                           [&](size_t k) { return fqz_size_lower_bound(C.fqz[k]); });
+                prune_plan(C, FAM_SEQ, SEQ10, SEQ14B, C.seq_b,
+                           [&](size_t k) { return seq_size_lower_bound(C.seq[k]); });
             }
-            std::exception_ptr ferr;
-            std::thread tf = on(ga, ferr, [&] { if (!fq.empty()) fqz_encode_finish(ga, fq, &skip_f); });
-            try {
-                FQZ5_HIP(hipSetDevice(gb.device));
-                if (!sq.empty()) seq_encode_finish(gb, sq, &skip_s);
-            } catch (...) {
-                tf.join();
-                throw;
-            }
-            tf.join();
-            if (ferr) std::rethrow_exception(ferr);
-            t_sess.fqz_skip.insert(t_sess.fqz_skip.end(), skip_f.begin(), skip_f.end());
-            t_sess.seq_skip.insert(t_sess.seq_skip.end(), skip_s.begin(), skip_s.end());
-            for (size_t k = 0; k < fq.size(); k++) {
-                t_sess.fqz_lb.push_back(skip_f[k] ? fqz_size_lower_bound(fq[k]) : 0);
-                t_sess.fqz_ub.push_back(skip_f[k] ? fqz_size_upper_bound(fq[k]) : 0);
-            }
-            for (size_t k = 0; k < sq.size(); k++) {
-                t_sess.seq_lb.push_back(skip_s[k] ? seq_size_lower_bound(sq[k]) : 0);
-                t_sess.seq_ub.push_back(skip_s[k] ? seq_size_upper_bound(sq[k]) : 0);
-            }
-            g_fqz_tried += fq.size() + sq.size();
-            for (char c : skip_f) g_fqz_pruned += c ? 1 : 0;
-            for (char c : skip_s) g_fqz_pruned += c ? 1 : 0;
-        } else {
-            join_stripes();
-            add_lzp3(g, secs, lzp_sec, reqs, t_sess.req_of);
-            compress_batch(g, reqs);
-            if (staged) stage2(nullptr);
-            encode_name_jobs(g, secs, name_sec, name_meth, t_sess.names);
-            if (!fq.empty()) fqz_encode_batch(g, fq);
-            if (!sq.empty()) seq_encode_batch(g, sq);
-            t_sess.fqz_lb.assign(fq.size(), 0);
-            t_sess.seq_lb.assign(sq.size(), 0);
-            t_sess.fqz_ub.assign(fq.size(), 0);
-            t_sess.seq_ub.assign(sq.size(), 0);
-            t_sess.fqz_skip.assign(fq.size(), 0);
-            t_sess.seq_skip.assign(sq.size(), 0);
-            g_fqz_tried += fq.size() + sq.size();
-        }
+        };
+        t_sess.aux = run_candidates(C, secs, g, true, hk, "sections_try", t0);
+        g_fqz_tried += C.fqz.size() + C.seq.size();
+        for (const Bound &b : C.fqz_b) g_fqz_pruned += b.skip ? 1 : 0;
+        for (const Bound &b : C.seq_b) g_fqz_pruned += b.skip ? 1 : 0;
         t_sess.open = true;
         if (step_trace())
             std::fprintf(stderr, "sections_try: %.1f ms (device / pinned allocations so far %llu, "
                          "frees %llu)\n", now_ms() - t0,
                          (unsigned long long)ChunkPool::alloc_calls().load(),
                          (unsigned long long)ChunkPool::free_calls().load());
-        // sizes as compress_with_methods sees them: UINT_MAX when not run,
-        // 0 when the codec returned NULL (out_len = *out_size = 0); a
-        // skipped candidate's lower bound here, its upper bound in `upper`
+        // a skipped candidate's lower bound in `sizes`, its upper bound in `upper`
         t_sess.upper.assign(size_t(nsec) * FQZ5_M_LAST, 0);
         for (int i = 0; i < nsec; i++) {
-            // encode_names returns NULL without writing *out_size, so a
-            // failing name candidate is seen with the size the previous name
-            // candidate of this section wrote (fqzcomp5.c:2036-2044, :1433-
-            // 1440); never strictly the best, but it enters the trial's
-            // totals (metrics_update) and can win the later blocks
             uint32_t stale = UINT32_MAX;
-            for (int m = 0; m < FQZ5_M_LAST; m++) {
-                const int ri = t_sess.req_of[i][m], fi = t_sess.fqz_of[i][m];
-                const int si = t_sess.seq_of[i][m], ni = t_sess.name_of[i][m];
-                uint32_t sz = UINT32_MAX;
-                if (ri >= 0) sz = reqs[ri].ok ? layout_size(reqs[ri].out) : 0;
-                // a name candidate's size is its whole section (encode_names'
-                // *out_size)
-                if (ni >= 0) {
-                    if (t_sess.names[size_t(ni)].ok)
-                        stale = sz = uint32_t(t_sess.names[size_t(ni)].out.size());
-                    else
-                        sz = stale;
-                }
-                if (si >= 0) {
-                    const uint64_t lb = t_sess.seq_lb[size_t(si)];   // pruned: its lower bound
-                    sz = t_sess.seq[size_t(si)].ok ? layout_size(t_sess.seq[size_t(si)].out)
-                         : lb ? uint32_t(std::min<uint64_t>(lb, UINT32_MAX - 1)) : 0;
-                }
-                if (fi >= 0) {
-                    const uint64_t lb = t_sess.fqz_lb[size_t(fi)];   // pruned: its lower bound
-                    sz = t_sess.fqz[size_t(fi)].ok ? layout_size(t_sess.fqz[size_t(fi)].out)
-                         : lb ? uint32_t(std::min<uint64_t>(lb, UINT32_MAX - 1)) : 0;
-                }
-                uint32_t up = sz;
-                if (si >= 0 && !t_sess.seq[size_t(si)].ok && t_sess.seq_ub[size_t(si)])
-                    up = uint32_t(std::min<uint64_t>(t_sess.seq_ub[size_t(si)], UINT32_MAX - 1));
-                if (fi >= 0 && !t_sess.fqz[size_t(fi)].ok && t_sess.fqz_ub[size_t(fi)])
-                    up = uint32_t(std::min<uint64_t>(t_sess.fqz_ub[size_t(fi)], UINT32_MAX - 1));
-                sizes[size_t(i) * FQZ5_M_LAST + m] = sz;
-                t_sess.upper[size_t(i) * FQZ5_M_LAST + m] = up;
-            }
+            for (int m = 0; m < FQZ5_M_LAST; m++)
+                sizes[size_t(i) * FQZ5_M_LAST + m] =
+                    C.size(i, m, &t_sess.upper[size_t(i) * FQZ5_M_LAST + m], &stale);
         }
         return 0;
     } catch (const std::exception &e) {
@@ -1000,111 +1036,29 @@ int fqz5_sections_commit(const fqz5_section *secs, int nsec, const int32_t *meth
     const double t0 = step_trace() ? now_ms() : 0;
     try {
         GpuCtx &g = gpu();
-        if (!t_sess.open || int(t_sess.req_of.size()) != nsec)
+        if (!t_sess.open || t_sess.c.nsec != nsec)
             throw GpuError("fqz5_sections_commit: no matching fqz5_sections_try");
-        // sections outside the trial: their one method, encoded now
-        std::vector<CompressReq> late;
-        std::vector<int> late_of(nsec, -1), late_fqz_of(nsec, -1), late_seq_of(nsec, -1);
-        std::vector<FqzEncReq> late_fqz;
-        std::vector<SeqEncReq> late_seq;
-        std::vector<int> late_lzp;
-        std::vector<std::vector<int>> late_lzp_of(nsec, std::vector<int>(FQZ5_M_LAST, -1));
-        std::vector<int> late_name_sec, late_name_meth, late_name_of(nsec, -1);
-        // a candidate the session tried with its range chain skipped (a
-        // bounds-only try or a pruned one) has no bytes: coded now, as a
-        // method the session did not try
-        auto coded_fqz = [&](int i, int m) {
-            const int f = t_sess.fqz_of[i][m];
-            return f >= 0 && !(size_t(f) < t_sess.fqz_skip.size() && t_sess.fqz_skip[size_t(f)]);
-        };
-        auto coded_seq = [&](int i, int m) {
-            const int q = t_sess.seq_of[i][m];
-            return q >= 0 && !(size_t(q) < t_sess.seq_skip.size() && t_sess.seq_skip[size_t(q)]);
-        };
+        const Candidates &C = t_sess.c;
         for (int i = 0; i < nsec; i++)                // a staged try's picks the replay overturned
             if (size_t(i) < t_sess.predicted.size() && t_sess.predicted[size_t(i)] >= 0 &&
                 t_sess.predicted[size_t(i)] != methods[i])
                 g_staged_n[2]++;
+        // The late set: sections outside the trial, their one method encoded
+        // now.  A candidate the session tried with its range chain skipped (a
+        // bounds-only try or a pruned one) has no bytes: coded now, as a
+        // method the session did not try.  A method that does not fit its
+        // section is left out (status -1 below), LZP3 on anything but a
+        // sequence section included (fqz5_decode_sections reads it only there).
+        std::vector<uint32_t> late_mask(size_t(std::max(nsec, 0)), 0);
         for (int i = 0; i < nsec; i++) {
             const int m = methods[i];
-            if (m <= 0 || m >= FQZ5_M_LAST || t_sess.req_of[i][m] >= 0 || coded_fqz(i, m) ||
-                coded_seq(i, m) || t_sess.name_of[i][m] >= 0)
-                continue;
-            if (is_name_method(m) && secs[i].sec == FQZ5_SEC_NAME) {
-                late_name_of[i] = int(late_name_sec.size());
-                late_name_sec.push_back(i);
-                late_name_meth.push_back(m);
-                continue;
-            }
-            if (is_seqcm(m) && secs[i].sec == FQZ5_SEC_SEQ && secs[i].rec_len) {
-                late_seq_of[i] = int(late_seq.size());
-                late_seq.push_back(seq_req(secs[i], m));
-                continue;
-            }
-            if (is_fqz(m) && secs[i].sec == FQZ5_SEC_QUAL && secs[i].rec_len) {
-                late_fqz_of[i] = int(late_fqz.size());
-                late_fqz.push_back(fqz_req(secs[i], m, t_sess.recs));
-                continue;
-            }
-            if (m == LZP3 && secs[i].sec == FQZ5_SEC_SEQ) {
-                late_lzp.push_back(i);
-                continue;
-            }
-            if (!(RANS_MASK & (1u << m)) || (m == RANSXN1 && !secs[i].fixed_len)) continue;
-            CompressReq r;
-            r.d_in = secs[i].in;
-            r.n = secs[i].in_size;
-            r.order = method_order(m, secs[i].fixed_len);
-            r.cap = compress_bound(r.n, r.order);
-            late_of[i] = int(late.size());
-            late.push_back(std::move(r));
+            if (m <= 0 || m >= FQZ5_M_LAST || C.coded(i, m)) continue;
+            if (m == LZP3 && secs[i].sec != FQZ5_SEC_SEQ) continue;
+            late_mask[size_t(i)] = 1u << m;
         }
-        // The late fqz encodes (-5 Illumina: every block's quality section;
-        // their range chains, ~1.2 s for a 100 MB block, are the commit's
-        // long pole) start first, in groups on the helper contexts (the
-        // sequence models' ones, idle now), so that each group's chains start
-        // when its own model pass is done, and the other late encodes run
-        // beside them on this thread.
-        static const bool no_aux = std::getenv("FQZ5_NO_AUX") != nullptr;
-        std::vector<std::vector<FqzEncReq>> fgrp;
-        std::vector<std::exception_ptr> ferr;
-        std::vector<std::thread> fth;
-        struct JoinAll {
-            std::vector<std::thread> &t;
-            ~JoinAll() { for (auto &x : t) if (x.joinable()) x.join(); }
-        } join_f{fth};
-        const bool fqz_aux = !late_fqz.empty() && !no_aux;
-        if (fqz_aux) {
-            const size_t ng = std::min<size_t>(late_fqz.size(), size_t(AUX_NSEQ));
-            fgrp.resize(ng);
-            ferr.resize(ng);
-            for (size_t k = 0; k < late_fqz.size(); k++) fgrp[k % ng].push_back(std::move(late_fqz[k]));
-            for (size_t q = 0; q < ng; q++) {
-                GpuCtx &c = gpu_aux(int(AUX_SEQ0 + q));
-                fth.emplace_back([&c, &grp = fgrp[q], &e = ferr[q]] {
-                    try {
-                        FQZ5_HIP(hipSetDevice(c.device));
-                        fqz_encode_batch(c, grp);
-                    } catch (...) {
-                        e = std::current_exception();
-                    }
-                });
-            }
-        }
-        add_lzp3(g, secs, late_lzp, late, late_lzp_of);
-        for (int i : late_lzp) late_of[i] = late_lzp_of[size_t(i)][LZP3];
-        if (!late.empty()) compress_batch(g, late);
-        if (!late_fqz.empty() && !fqz_aux) fqz_encode_batch(g, late_fqz);
-        if (!late_seq.empty()) seq_encode_batch(g, late_seq);
-        std::vector<NameEnc> late_names;
-        encode_name_jobs(g, secs, late_name_sec, late_name_meth, late_names);
-        if (fqz_aux) {
-            for (auto &t : fth) t.join();
-            for (auto &e : ferr)
-                if (e) std::rethrow_exception(e);
-            const size_t ng = fgrp.size();
-            for (size_t k = 0; k < late_fqz.size(); k++) late_fqz[k] = std::move(fgrp[k % ng][k / ng]);
-        }
+        Candidates late(nsec);
+        collect(late, secs, late_mask.data());
+        const bool late_aux = run_candidates(late, secs, g, false, RunHooks(), "sections_commit", t0);
         std::vector<const Layout *> ls;
         std::vector<uint8_t *> dsts;
         std::vector<Layout> framed(nsec);
@@ -1112,14 +1066,9 @@ int fqz5_sections_commit(const fqz5_section *secs, int nsec, const int32_t *meth
             const fqz5_section &S = secs[i];
             fqz5_section_result &R = res[i];
             const int m = methods[i];
-            const int ri = (m > 0 && m < FQZ5_M_LAST) ? t_sess.req_of[i][m] : -1;
-            const int fi = (m > 0 && m < FQZ5_M_LAST) ? t_sess.fqz_of[i][m] : -1;
-            const int si = (m > 0 && m < FQZ5_M_LAST) ? t_sess.seq_of[i][m] : -1;
-            const int ni = (m > 0 && m < FQZ5_M_LAST) ? t_sess.name_of[i][m] : -1;
+            // the session's bytes, else the late set's
             if (S.sec == FQZ5_SEC_NAME) {             // encode_names' bytes, unframed
-                const NameEnc *E = ni >= 0 ? &t_sess.names[size_t(ni)]
-                                   : late_name_of[i] >= 0 ? &late_names[size_t(late_name_of[i])]
-                                                          : nullptr;
+                const NameEnc *E = C.name(i, m) ? C.name(i, m) : late.name(i, m);
                 R.method = m;
                 R.strat = is_name_method(m) ? name_strat(m) : 0;
                 R.status = -1;
@@ -1136,13 +1085,7 @@ int fqz5_sections_commit(const fqz5_section *secs, int nsec, const int32_t *meth
                 R.status = 0;
                 continue;
             }
-            const Layout *lay = nullptr;
-            if (ri >= 0 && t_sess.reqs[ri].ok) lay = &t_sess.reqs[ri].out;
-            if (late_of[i] >= 0 && late[late_of[i]].ok) lay = &late[late_of[i]].out;
-            if (fi >= 0 && t_sess.fqz[size_t(fi)].ok) lay = &t_sess.fqz[size_t(fi)].out;
-            if (late_fqz_of[i] >= 0 && late_fqz[late_fqz_of[i]].ok) lay = &late_fqz[late_fqz_of[i]].out;
-            if (si >= 0 && t_sess.seq[size_t(si)].ok) lay = &t_sess.seq[size_t(si)].out;
-            if (late_seq_of[i] >= 0 && late_seq[late_seq_of[i]].ok) lay = &late_seq[late_seq_of[i]].out;
+            const Layout *lay = C.layout(i, m) ? C.layout(i, m) : late.layout(i, m);
             R.method = m;
             // compress_with_methods' *strat (fqzcomp5.c:1994-2069)
             R.strat = is_fqz(m) ? 1 : is_seqcm(m) ? seq_strat(m) : m == LZP3 ? LZP3 : 0;
@@ -1172,7 +1115,7 @@ int fqz5_sections_commit(const fqz5_section *secs, int nsec, const int32_t *meth
         const double t3 = step_trace() ? now_ms() : 0;
         // the fqz candidates of the try live in the aux arena: rewind it too,
         // or every step's trial buffers take fresh chunks (the r01 bench OOM)
-        if (t_sess.aux || fqz_aux) gpu_aux_reset_all();
+        if (t_sess.aux || late_aux) gpu_aux_reset_all();
         // the session's host buffers (candidate tables, layouts, the name
         // candidates' token streams: ~100 MB, mostly munmap) are freed by a
         // detached thread, off the caller's path; nothing refers to them now
@@ -1188,6 +1131,7 @@ int fqz5_sections_commit(const fqz5_section *secs, int nsec, const int32_t *meth
         fqz5_set_error(e.what());
         t_sess = TrySession();
         try { gpu().reset(); } catch (...) {}
+        try { gpu_aux_reset_all(); } catch (...) {}   // (the late fqz groups' and the session's arenas)
         return -1;
     }
 }
@@ -1420,38 +1364,28 @@ int fqz5_decode_sections(const fqz5_section *secs, int nsec, fqz5_section_result
         // they count as a second hedging caller: the chains' copies take half
         // the CUs and the names' short kernels find the rest free (their
         // host rebuild needs no CU at all).
-        std::exception_ptr nerr;
         double t_names_up = 0;                        // (trace) the names' upload done
-        std::thread tn;
         GpuCtx *gn = nullptr;
         std::unique_ptr<HedgeShare> nshare;
+        host::Task tn;                                // (the helpers: joined on every exit)
         if (!nd.empty()) {
             gn = &gpu_aux(AUX_NAMES);
             nshare = std::make_unique<HedgeShare>(size_t(g.cus));
-            tn = std::thread([&] {
-                try {
-                    FQZ5_HIP(hipSetDevice(gn->device));
-                    // each block's names to their section as soon as that
-                    // block is rebuilt, on the names context, while the
-                    // chains (and the later blocks' rebuilds) still run (after
-                    // them, on the main stream, -5 NovaSeq's 590 MB of names
-                    // added ~50 ms)
-                    names_decode_batch(*gn, nd, [&](size_t k) {
-                        if (nd[k].ok && nd[k].u_len)
-                            FQZ5_HIP(hipMemcpyAsync(secs[who_name[k]].out, nd[k].names,
-                                                    nd[k].u_len, hipMemcpyHostToDevice, gn->stream));
-                    });
-                    gn->sync();                       // (nd's buffers are the sources)
-                    if (trace) t_names_up = now_ms();
-                } catch (...) {
-                    nerr = std::current_exception();
-                }
+            tn = on_ctx(*gn, "decode_sections", t0, [&] {
+                // each block's names to their section as soon as that
+                // block is rebuilt, on the names context, while the
+                // chains (and the later blocks' rebuilds) still run (after
+                // them, on the main stream, -5 NovaSeq's 590 MB of names
+                // added ~50 ms)
+                names_decode_batch(*gn, nd, [&](size_t k) {
+                    if (nd[k].ok && nd[k].u_len)
+                        FQZ5_HIP(hipMemcpyAsync(secs[who_name[k]].out, nd[k].names,
+                                                nd[k].u_len, hipMemcpyHostToDevice, gn->stream));
+                });
+                gn->sync();                           // (nd's buffers are the sources)
+                if (trace) t_names_up = now_ms();
             });
         }
-        struct Join {                                 // joined on every exit
-            std::thread &t;
-            ~Join() { if (t.joinable()) t.join(); }
-        } join_names{tn};
         // GPU quality sections without a sequence context need nothing else
         // of this call: they decode on the fqz helper context from a thread
         // of their own, beside the rANS / LZP / sequence-model work, instead
@@ -1468,21 +1402,14 @@ int fqz5_decode_sections(const fqz5_section *secs, int nsec, fqz5_section_result
             is_early[k] = 1;
             early_longest = std::max<uint64_t>(early_longest, fqz[k].out_cap);
         }
-        std::exception_ptr ferr;
-        std::thread tf;
         GpuCtx *gf = nullptr;
+        host::Task tf;
         if (!fqz_early.empty()) {
-            gf = &gpu_aux(0);
-            tf = std::thread([&] {
-                try {
-                    FQZ5_HIP(hipSetDevice(gf->device));
-                    timed(host::CK_FQZ, true, early_longest, [&] { fqz_decode_batch(*gf, fqz_early); return true; });
-                } catch (...) {
-                    ferr = std::current_exception();
-                }
+            gf = &gpu_aux(AUX_FQZ);
+            tf = on_ctx(*gf, "decode_sections", t0, [&] {
+                timed(host::CK_FQZ, true, early_longest, [&] { fqz_decode_batch(*gf, fqz_early); return true; });
             });
         }
-        Join join_fqz{tf};
         // the GPU's sequence-model sections likewise (their own helper context)
         std::vector<SeqDecReq> seq_gpu;
         std::vector<size_t> seq_gpu_of;
@@ -1493,21 +1420,14 @@ int fqz5_decode_sections(const fqz5_section *secs, int nsec, fqz5_section_result
                 seq_gpu_of.push_back(m);
                 seq_longest = std::max<uint64_t>(seq_longest, seqd[m].n);
             }
-        std::exception_ptr serr;
-        std::thread ts;
         GpuCtx *gs = nullptr;
+        host::Task ts;
         if (!seq_gpu.empty()) {
             gs = &gpu_aux(AUX_SEQ0);
-            ts = std::thread([&] {
-                try {
-                    FQZ5_HIP(hipSetDevice(gs->device));
-                    timed(host::CK_SEQ, true, seq_longest, [&] { seq_decode_batch(*gs, seq_gpu); return true; });
-                } catch (...) {
-                    serr = std::current_exception();
-                }
+            ts = on_ctx(*gs, "decode_sections", t0, [&] {
+                timed(host::CK_SEQ, true, seq_longest, [&] { seq_decode_batch(*gs, seq_gpu); return true; });
             });
         }
-        Join join_seq{ts};
         // the rANS batch's long chains share the cores with the chains
         // started above: it gets the cores those leave idle (the late
         // quality chains run after it), so that no more than host::threads()
@@ -1536,8 +1456,7 @@ int fqz5_decode_sections(const fqz5_section *secs, int nsec, fqz5_section_result
                 R.usize = run[k].out_len;
             }
         }
-        if (ts.joinable()) ts.join();
-        if (serr) std::rethrow_exception(serr);
+        ts.join();
         for (size_t i = 0; i < seq_gpu.size(); i++) seqd[seq_gpu_of[i]] = seq_gpu[i];
         // after the rANS and sequence sections: a quality section's sequence
         // context may be the output of this call's sequence section (a GPU
@@ -1557,8 +1476,7 @@ int fqz5_decode_sections(const fqz5_section *secs, int nsec, fqz5_section_result
                 for (size_t k = 0; k < late.size(); k++) fqz[late_of[k]] = late[k];
             }
         }
-        if (tf.joinable()) tf.join();
-        if (ferr) std::rethrow_exception(ferr);
+        tf.join();
         for (size_t k = 0; k < fqz_early.size(); k++) fqz[early_of[k]] = fqz_early[k];
         if (!hc.empty()) {
             hjobs.join();
@@ -1614,9 +1532,8 @@ int fqz5_decode_sections(const fqz5_section *secs, int nsec, fqz5_section_result
             }
         }
         const double t_hc = trace ? now_ms() : 0;
-        if (tn.joinable()) tn.join();
+        tn.join();
         nshare.reset();
-        if (nerr) std::rethrow_exception(nerr);
         const double t_nj = trace ? now_ms() : 0;
         for (size_t k = 0; k < nd.size(); k++) {
             fqz5_section_result &R = res[who_name[k]];

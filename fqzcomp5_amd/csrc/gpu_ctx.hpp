@@ -650,7 +650,8 @@ GpuCtx &gpu();
 // and a rewind of every one that exists.
 constexpr int AUX_CTXS = 11;  // 0 fqz, 1 LZP3, 2..7 sequence models, 8 stripes, 9 names,
                               // 10 plain rANS candidates
-constexpr int AUX_SEQ0 = 2, AUX_NSEQ = 6, AUX_STRIPES = 8, AUX_NAMES = 9, AUX_PLAIN = 10;
+constexpr int AUX_FQZ = 0, AUX_LZP = 1, AUX_SEQ0 = 2, AUX_NSEQ = 6, AUX_STRIPES = 8, AUX_NAMES = 9,
+              AUX_PLAIN = 10;
 GpuCtx &gpu_aux(int k = 0);
 void gpu_aux_reset_all();
 // After synchronising them, free the device arenas of the calling thread's

@@ -1,7 +1,8 @@
 // host_sched.hpp — the host cores beside the GPU: how many threads the
 // library's pools use, which serial chains run on a core and which on the GPU
 // (the cost model, plan, place), the pools' one worker loop (Jobs,
-// parallel_for) and the clocks of the step trace.  No HIP.
+// parallel_for), one function on a thread of its own (Task) and the clocks of
+// the step trace.  No HIP.
 #pragma once
 #include <time.h>
 #include <atomic>
@@ -10,8 +11,10 @@
 #include <cstdint>
 #include <exception>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <thread>
+#include <utility>
 #include <vector>
 
 namespace fqz5 {
@@ -103,7 +106,46 @@ class Jobs {
     std::vector<std::thread> th_;
 };
 
-// The same, blocking: the caller works too and gets the first exception of fn;
+// Jobs' counterpart for a single function: fn() on a thread of its own, started
+// by the constructor; an empty fn starts none.  An exception of fn is kept:
+// join() waits and rethrows it (once), the destructor only waits, so a scope
+// that unwinds leaves no thread of its own behind.  What fn refers to must be
+// declared before the Task.
+class Task {
+  public:
+    Task() = default;
+    explicit Task(std::function<void()> fn) {
+        if (!fn) return;
+        err_ = std::make_unique<std::exception_ptr>();
+        th_ = std::thread([fn = std::move(fn), e = err_.get()] {
+            try {
+                fn();
+            } catch (...) {
+                *e = std::current_exception();
+            }
+        });
+    }
+    Task(Task &&) = default;
+    Task &operator=(Task &&o) {                 // (waits for its own function first)
+        wait();
+        err_ = std::move(o.err_);
+        th_ = std::move(o.th_);
+        return *this;
+    }
+    bool running() const { return th_.joinable(); }   // started and not waited for yet
+    void join() {
+        wait();
+        if (err_ && *err_) std::rethrow_exception(std::exchange(*err_, nullptr));
+    }
+    ~Task() { wait(); }
+
+  private:
+    void wait() { if (th_.joinable()) th_.join(); }
+    std::unique_ptr<std::exception_ptr> err_;
+    std::thread th_;
+};
+
+// Jobs, blocking: the caller works too and gets the first exception of fn;
 // fn(i) must touch item i only.  Fewer than serial_below items, or one host
 // thread, run on the caller alone.
 void parallel_for(size_t n, const std::function<void(size_t)> &fn, size_t grain, size_t serial_below);

@@ -270,49 +270,38 @@ void names_encode_batch(GpuCtx &g, std::vector<NameEnc> &jobs,
         lz1_host.push_back(E.comments.data());
     }
     double t_early = 0;
-    std::exception_ptr err0;
-    std::thread gpu_early([&] {
-        try {
-            // a new thread starts on device 0: g's arena may grow (hipMalloc
-            // on the current device) and must land on g's device
-            FQZ5_HIP(hipSetDevice(g.device));
-            for (size_t k : early) {
-                name_prepare(h_names[k], lens[k], 0, name_level(methods[k]), jobs[k]);
-                name_add_lzp(g, jobs[k], d_names[k], lz0);
-            }
-            if (!lz0.empty()) lzp_encode_batch(g, lz0);
-            for (size_t i = 0; i < lz1.size(); i++)
-                lz1[i].d_in = g.upload(reinterpret_cast<const uint8_t *>(lz1_host[i]), lz1[i].n);
-            if (!lz1.empty()) lzp_encode_batch(g, lz1);
-            for (size_t k : early) name_add_requests(g, jobs[k], lz0, rq0);
-            if (!rq0.empty()) compress_batch(g, rq0);
-            if (step_trace()) t_early = now_ms();
-        } catch (...) {
-            err0 = std::current_exception();
+    host::Task gpu_early([&] {
+        // a new thread starts on device 0: g's arena may grow (hipMalloc
+        // on the current device) and must land on g's device
+        FQZ5_HIP(hipSetDevice(g.device));
+        for (size_t k : early) {
+            name_prepare(h_names[k], lens[k], 0, name_level(methods[k]), jobs[k]);
+            name_add_lzp(g, jobs[k], d_names[k], lz0);
         }
+        if (!lz0.empty()) lzp_encode_batch(g, lz0);
+        for (size_t i = 0; i < lz1.size(); i++)
+            lz1[i].d_in = g.upload(reinterpret_cast<const uint8_t *>(lz1_host[i]), lz1[i].n);
+        if (!lz1.empty()) lzp_encode_batch(g, lz1);
+        for (size_t k : early) name_add_requests(g, jobs[k], lz0, rq0);
+        if (!rq0.empty()) compress_batch(g, rq0);
+        if (step_trace()) t_early = now_ms();
     });
     // fewer host-searched sections than host threads: each tokenises on two
     // (its trie searches ahead on the second), so its names take ~60 % as long
     const size_t hw = size_t(host::threads());
     const bool pipelined = on_host < hw;
-    try {
-        on_threads(groups.size(), [&](size_t i) {
-            const std::vector<size_t> &gr = groups[i];
-            const size_t k = gr[0];
-            name_tokenise(jobs[k], pipelined, sj[i].ok ? sj[i].found.data() : nullptr);
-            for (size_t x = 1; x < gr.size(); x++) {
-                NameEnc &E = jobs[gr[x]];
-                E = jobs[k];
-                E.level = E.tok.level = name_level(methods[gr[x]]);
-            }
-        });
-    } catch (...) {
-        gpu_early.join();
-        throw;
-    }
+    on_threads(groups.size(), [&](size_t i) {
+        const std::vector<size_t> &gr = groups[i];
+        const size_t k = gr[0];
+        name_tokenise(jobs[k], pipelined, sj[i].ok ? sj[i].found.data() : nullptr);
+        for (size_t x = 1; x < gr.size(); x++) {
+            NameEnc &E = jobs[gr[x]];
+            E = jobs[k];
+            E.level = E.tok.level = name_level(methods[gr[x]]);
+        }
+    });
     const double t1 = step_trace() ? now_ms() : 0;
     gpu_early.join();
-    if (err0) std::rethrow_exception(err0);
     const double t1b = step_trace() ? now_ms() : 0;
     const double t2 = t1b;
     for (const auto &gr : groups)

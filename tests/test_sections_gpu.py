@@ -194,3 +194,121 @@ def test_run_bounds_first_equals_run(level, kind, nreads, blk):
     assert all(r.status == 0 for r in dres)
     torch.cuda.synchronize()
     assert run_b.roundtrip_ok()
+
+
+# ---- the try's and the commit's candidates, family by family ---------------
+# The shape test_staged_try_gpu.py uses for "every chain on the GPU", and its
+# 2.7 MB one (sections over 2^20 B: the plain O0/O1 requests would split off).
+def _blocks(nreads=3600, blk=200_000):
+    reads = synth.illumina(nreads, seed=21)
+    blocks = synth.split_blocks(reads, blk)[:6]
+    assert len(blocks) == 6
+    return reads, blocks
+
+
+def _try_commit(secs, masks, methods):
+    """One unstaged try of masks[i] per section and the commit of `methods`:
+    (the sizes matrix, the results)."""
+    sizes = S.sections_try(secs, np.asarray(masks, np.uint32)).copy()
+    return sizes, S.sections_commit(secs, np.asarray(methods, np.int32))
+
+
+def _same_sections(run_a, res_a, run_b, res_b):
+    assert [(r.method, r.strat, r.clen, r.usize) for r in res_a] == \
+        [(r.method, r.strat, r.clen, r.usize) for r in res_b]
+    for i in range(len(res_a)):
+        assert run_a.chosen(res_a, i) == run_b.chosen(res_b, i), i
+
+
+def _decodes_back(run, res):
+    dres = S.decode(run.dec_secs(res))
+    assert all(r.status == 0 for r in dres)
+    torch.cuda.synchronize()
+    assert run.roundtrip_ok()
+
+
+def test_late_equals_tried():
+    """A method's bytes are the same whether the try coded them or the commit
+    codes them late, for every coder family: the same method vector committed
+    after a try of the full -5 masks, and after a try of one plain rANS method
+    (the first name method) per section, which leaves the chosen names, SEQ1x,
+    FQZx, LZP3, RANSXN1 and packed rANS streams to the commit."""
+    reads, blocks = _blocks()
+    av = S.masks(5, True)
+    dev = torch.device("cuda", 0)
+    run_a, run_b = S.Run(reads, blocks, dev, names=True), S.Run(reads, blocks, dev, names=True)
+    name_m = sorted(m for m in range(S.M_LAST) if int(av[S.SEC_NAME]) >> m & 1)
+    cycle = {S.SEC_NAME: name_m,
+             S.SEC_SEQ: [S.SEQ10, S.LZP3, S.RANS129, S.SEQ12B, S.RANS193, S.RANS1],
+             S.SEC_QUAL: [S.FQZ1, S.RANSXN1, S.RANS193, S.FQZ3, S.RANS129, S.RANS1]}
+    methods = [cycle[sp[0]][sp[4] % len(cycle[sp[0]])] for sp in run_a.spans]
+    assert all(int(av[sp[0]]) >> m & 1 for sp, m in zip(run_a.spans, methods))
+    # every family, and coded late in the second run
+    one = {S.SEC_NAME: name_m[0], S.SEC_SEQ: S.RANS0, S.SEC_QUAL: S.RANS0}
+    late = {m for sp, m in zip(run_a.spans, methods) if m != one[sp[0]]}
+    assert late & set(name_m) and late & set(S.SEQ_PARAMS) and late & {S.FQZ1, S.FQZ3}
+    assert S.LZP3 in late and late & {S.RANS129, S.RANS193}
+    assert any(m == S.RANSXN1 and sp[3] > 0 for sp, m in zip(run_a.spans, methods))
+    _, res_a = _try_commit(run_a.enc_secs(), [av[sp[0]] for sp in run_a.spans], methods)
+    _, res_b = _try_commit(run_b.enc_secs(), [1 << one[sp[0]] for sp in run_b.spans], methods)
+    assert all(r.status == 0 for r in res_a) and all(r.status == 0 for r in res_b)
+    _same_sections(run_a, res_a, run_b, res_b)
+    _decodes_back(run_a, res_a)
+    _decodes_back(run_b, res_b)
+
+
+@pytest.mark.parametrize("nreads,blk", [(3600, 200_000), (52000, 2_700_000)])
+def test_try_without_helpers(nreads, blk):
+    """A try of plain rANS candidates only, without name sections, needs no
+    helper: its candidates are those of the full-mask try (sizes, and the
+    bytes of a method vector that cycles through them), also where sections of
+    2^20 B and more would split the plain O0/O1 requests off; and repeating it
+    does not grow the device arenas."""
+    reads, blocks = _blocks(nreads, blk)
+    av = S.masks(5, True)
+    dev = torch.device("cuda", 0)
+    run_a, run_b = S.Run(reads, blocks, dev, names=False), S.Run(reads, blocks, dev, names=False)
+    if blk > 1_000_000:
+        assert all(e - s >= 1 << 20 for sec, s, e, fl, k in run_a.spans)
+    plain = [S.RANS0, S.RANS1, S.RANS129, S.RANS193]
+    pmask = sum(1 << m for m in plain)
+    assert all(int(av[sp[0]]) & pmask == pmask for sp in run_a.spans)
+    methods = [plain[i % 4] for i in range(len(run_a.spans))]
+    sizes_a, res_a = _try_commit(run_a.enc_secs(), [av[sp[0]] for sp in run_a.spans], methods)
+    secs_b = run_b.enc_secs()
+    sizes_b, res_b = _try_commit(secs_b, [pmask] * len(secs_b), methods)
+    assert all(r.status == 0 for r in res_a) and all(r.status == 0 for r in res_b)
+    assert (sizes_b[:, plain] == sizes_a[:, plain]).all()
+    rest = [m for m in range(S.M_LAST) if m not in plain]
+    assert (sizes_b[:, rest] == 0xFFFFFFFF).all()
+    _same_sections(run_a, res_a, run_b, res_b)
+    _decodes_back(run_b, res_b)
+    held = lib.arena_bytes()
+    for _ in range(3):
+        _try_commit(secs_b, [pmask] * len(secs_b), methods)
+        assert lib.arena_bytes() == held
+
+
+def test_commit_method_that_does_not_fit():
+    """A method that does not fit its section at commit (an FQZ method on a
+    sequence section, a sequence model on a quality section, RANSXN1 without a
+    fixed length) leaves that section without bytes: status -1 and clen 0;
+    the other sections are coded."""
+    reads, blocks = _blocks()
+    run = S.Run(reads, blocks, torch.device("cuda", 0), names=False)
+    secs = run.enc_secs()
+    seq = [i for i, sp in enumerate(run.spans) if sp[0] == S.SEC_SEQ]
+    qual = [i for i, sp in enumerate(run.spans) if sp[0] == S.SEC_QUAL]
+    methods = [S.RANS1] * len(secs)
+    methods[seq[1]] = S.FQZ1
+    methods[qual[2]] = S.SEQ10
+    methods[qual[3]] = S.RANSXN1
+    secs[qual[3]].fixed_len = 0
+    bad = {seq[1], qual[2], qual[3]}
+    _, res = _try_commit(secs, [1 << S.RANS0] * len(secs), methods)
+    for i, r in enumerate(res):
+        assert r.method == methods[i] and r.usize == secs[i].in_size
+        if i in bad:
+            assert (r.status, r.clen) == (-1, 0), i
+        else:
+            assert r.status == 0 and r.clen > 0, i

@@ -8,8 +8,10 @@
 //   FQZ5_HOST_THREADS=4 check
 //
 // It checks place() against its rule and against plan(), measured() against
-// chain_ns(), and the two front ends of the worker loop (parallel_for, Jobs):
-// every index once, the thread caps, and what a throwing item does.  Exit 0
+// chain_ns(), the two front ends of the worker loop (parallel_for, Jobs):
+// every index once, the thread caps, and what a throwing item does; and Task:
+// when it starts a thread, where its function's exception goes, and that a
+// scope never leaves one running.  Exit 0
 // and nothing on stderr: everything as expected (tests/test_host_sched.py).
 #include <algorithm>
 #include <atomic>
@@ -203,12 +205,72 @@ static void check_jobs() {
     CHECK(ran == 20);
 }
 
+// one function on a thread of its own
+static void check_task() {
+    std::atomic<int> ran{0};
+    {
+        Task t([&] { ran++; });
+        CHECK(t.running());
+        t.join();
+        CHECK(!t.running());
+        t.join();                                 // (nothing left to wait for)
+    }
+    CHECK(ran == 1);
+    // an empty function starts no thread
+    Task none{std::function<void()>()};
+    CHECK(!none.running());
+    none.join();
+    CHECK(!Task().running());
+    // an exception comes out of join() exactly once
+    {
+        Task t([] { throw Boom(); });
+        int thrown = 0;
+        try { t.join(); } catch (const Boom &) { thrown++; }
+        try { t.join(); } catch (const Boom &) { thrown++; }
+        CHECK(thrown == 1);
+    }
+    // the destructor after an unjoined failure waits and stays quiet
+    {
+        Task quiet([&] { ran++; throw Boom(); });
+    }
+    CHECK(ran == 2);
+    // a moved task keeps its function's exception; assignment waits for the old one
+    {
+        Task a([&] { ran++; });
+        a = Task([] { throw Boom(); });
+        CHECK(ran == 3);
+        Task b(std::move(a));
+        CHECK(!a.running() && b.running());
+        bool thrown = false;
+        try { b.join(); } catch (const Boom &) { thrown = true; }
+        CHECK(thrown);
+        a.join();
+    }
+    // a scope that unwinds from an exception of its own while two helpers
+    // still run: both have finished (the flag is the last thing each sets)
+    // before the catch block runs
+    std::atomic<int> go{0}, done_a{0}, done_b{0};
+    bool caught = false;
+    try {
+        Task a([&] { while (!go) std::this_thread::yield(); done_a = 1; });
+        Task b([&] { while (!go) std::this_thread::yield(); done_b = 1; throw Boom(); });
+        CHECK(done_a == 0 && done_b == 0);        // (both wait for `go`)
+        go = 1;
+        throw std::runtime_error("the scope's own");
+    } catch (const std::runtime_error &e) {
+        caught = std::string(e.what()) == "the scope's own";
+        CHECK(done_a == 1 && done_b == 1);
+    }
+    CHECK(caught);
+}
+
 int main() {
     check_place_rule();                 // (first: it reads the priors)
     check_place_against_plan();
     check_measured();
     check_parallel_for();
     check_jobs();
+    check_task();
     if (g_bad) return 1;
     std::printf("host_sched_check: ok (%d host threads)\n", threads());
     return 0;
