@@ -14,6 +14,8 @@
 //                   grid-strides over the tiles, skipping those in which no
 //                   record can have a position inside its window.
 //   k_stats_bin     read_qual and read_gc from the per-read sums.
+// (The tiles, the record ends in LDS and the loads are stats_tile.hpp's,
+// shared with filter.hip.)
 // The record that owns a base comes from the records' ends: the host gives
 // each tile its first record (a merge of the ends with the tile grid), the
 // workgroup stages the tile's ends into LDS, a lane searches them once for
@@ -34,6 +36,7 @@
 #include "../../include/fqz5_fastq.h"
 #include "gpu_ctx.hpp"
 #include "name_match.hpp"
+#include "stats_tile.hpp"
 
 namespace fqz5 {
 GpuCtx &gpu();
@@ -53,12 +56,8 @@ struct fqz5_stats {
 namespace fqz5 {
 namespace {
 
-constexpr uint32_t ST_TILE = 4096;              // bases per tile
-constexpr uint32_t ST_THREADS = 256;
-constexpr uint32_t ST_KCAP = 2048;              // a tile's record ends kept in LDS
 constexpr uint32_t ST_WIN_CELLS = 64;           // cycles x mates of one cycle window
 constexpr uint32_t ST_CYCLES_MAX = 1u << 16;
-constexpr uint64_t ST_LAUNCH_TILES = (1ull << 31) / ST_TILE;   // bases per launch <= 2^31
 // words of one mate's block
 constexpr uint64_t ST_RECORDS = 0, ST_BASES = 1, ST_QUAL_RECORDS = 2, ST_EMPTY = 3, ST_BASE = 4,
                    ST_QUAL = 260, ST_READ_QUAL = 516, ST_READ_GC = 772, ST_CYCLE_BASE = 873;
@@ -74,74 +73,6 @@ __host__ __device__ inline uint32_t base_class(uint32_t c) {
     const uint32_t f = c | 0x20u;
     return f == 'a' ? 0 : f == 'c' ? 1 : f == 'g' ? 2 : f == 't' ? 3 : f == 'n' ? 4 : 5;
 }
-__host__ __device__ inline uint32_t is_gc(uint32_t c) {
-    const uint32_t f = c | 0x20u;
-    return f == 'c' || f == 'g';
-}
-
-// the 16 bytes at s + a: one load where they lie wholly inside [0, len)
-__device__ inline uint4 load16(const uint8_t *s, uint64_t len, int64_t a) {
-    if (a >= 0 && uint64_t(a) + 16 <= len) return *reinterpret_cast<const uint4 *>(s + a);
-    uint32_t w[4] = {0, 0, 0, 0};
-    for (int k = 0; k < 16; k++)
-        if (a + k >= 0 && uint64_t(a + k) < len)
-            w[k >> 2] |= uint32_t(s[a + k]) << (8 * (k & 3));
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-// One tile as its workgroup sees it: the records r0 .. r0 + nrt - 1 are those
-// that can own one of its n bases; their ends, relative to the tile and
-// clipped to ST_TILE, are in `lend` for the first ST_KCAP of them and read
-// from the ends array beyond (tiles of more than 2048 records).
-struct Tile {
-    const uint64_t *end;
-    const uint32_t *lend;
-    uint64_t t0;
-    uint32_t n, r0, nrt;
-    int64_t start0;                             // where r0 starts, relative to the tile (<= 0)
-
-    __device__ void open(const uint64_t *ends, const uint32_t *tf, uint32_t nrec, uint64_t seq_len,
-                         uint64_t t, uint32_t *lds) {
-        end = ends;
-        lend = lds;
-        t0 = t * ST_TILE;
-        n = uint32_t(seq_len - t0 < ST_TILE ? seq_len - t0 : ST_TILE);
-        r0 = tf[t];
-        const uint32_t r1 = tf[t + 1] < nrec - 1 ? tf[t + 1] : nrec - 1;
-        nrt = r1 - r0 + 1;
-        start0 = int64_t(r0 ? ends[r0 - 1] : 0) - int64_t(t0);
-    }
-    // (all threads, then a barrier)
-    __device__ void stage(uint32_t *lds) const {
-        const uint32_t k1 = nrt < ST_KCAP ? nrt : ST_KCAP;
-        for (uint32_t k = threadIdx.x; k < k1; k += ST_THREADS) {
-            const uint64_t e = end[r0 + k] - t0;
-            lds[k] = e < ST_TILE ? uint32_t(e) : ST_TILE;
-        }
-    }
-    __device__ uint32_t relend(uint32_t k) const {
-        if (k < ST_KCAP) return lend[k];
-        const uint64_t e = end[r0 + k] - t0;
-        return e < ST_TILE ? uint32_t(e) : ST_TILE;
-    }
-    // the record (index within the tile) that owns relative position q < n:
-    // the first whose end lies past q, so never an empty one
-    __device__ uint32_t owner(uint32_t q) const {
-        uint32_t lo = 0, hi = nrt - 1;          // (relend(nrt - 1) >= n > q)
-        while (lo < hi) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if (relend(mid) > q) hi = mid; else lo = mid + 1;
-        }
-        return lo;
-    }
-    __device__ int64_t start(uint32_t k) const { return k ? int64_t(relend(k - 1)) : start0; }
-};
-
-// a non-zero LDS cell into its u64 global cell
-__device__ inline void flush_cell(uint64_t *g, uint32_t v) {
-    if (v) atomicAdd(reinterpret_cast<unsigned long long *>(g), static_cast<unsigned long long>(v));
-}
-
 // base_counts, qual_counts, and per record the number of G/C bytes and the
 // sum of the qualities.  A lane walks the records across its chunk and adds a
 // record's partial sum once: to the tile's LDS cell of that record (flushed
@@ -411,14 +342,8 @@ int fqz5_stats_add(fqz5_stats *S, const uint8_t *d_seq, const uint8_t *d_qual, u
         const uint64_t *d_end = g.upload(end);
         const uint64_t tiles = (seq_len + ST_TILE - 1) / ST_TILE;
         if (tiles) {
-            // each tile's first record: the first whose end lies past the tile's start
-            std::vector<uint32_t> tf(size_t(tiles) + 1);
-            uint32_t r = 0, longest = 0;
-            for (uint64_t t = 0; t < tiles; t++) {
-                while (end[r] <= t * ST_TILE) r++;
-                tf[size_t(t)] = r;
-            }
-            tf[size_t(tiles)] = n - 1;
+            const std::vector<uint32_t> tf = tile_first(end, tiles);
+            uint32_t longest = 0;
             for (uint64_t k = 0; k < nrec; k++) longest = std::max(longest, h_lens[k]);
             const uint32_t *d_tf = g.upload(tf);
             const uint32_t ceff = std::min(S->cycles, longest);

@@ -41,6 +41,14 @@ fqzcomp5 writes, produced and read by this library alone.
                                      and quality sections decoded, histogrammed
                                      on the device (fqz5_stats_add); no names,
                                      no text, only the tables come back
+    filter_records(src, Filter(...)) / filter_file(src, dst, flt[, dst2=]) /
+    filter_bytes: records by read metrics (length, N count, mean quality,
+                                     low-quality share, GC, complexity), the
+                                     same pass with the sections the criteria
+                                     need as keys; summed and picked on the
+                                     device (fqz5_filter_match) -> the other
+                                     sections decoded for the blocks with kept
+                                     records only -> fqz5_fastq_format_list
 
 File layout (fqzcomp5.c:2563-2630, :2959-2969): "FQZ5\\1\\1\\0\\0", u64 index
 offset, the blocks, then "FQZ5IDX\\0", u32 nblocks and per block {u64 file
@@ -164,6 +172,16 @@ def _load():
         so.fqz5_stats_host.argtypes = [C.c_uint32, C.c_int, C.c_char_p, C.c_char_p, C.c_uint64,
                                        C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
                                        C.c_void_p]
+        so.fqz5_filter_tile.restype = C.c_uint32
+        so.fqz5_filter_tile.argtypes = []
+        so.fqz5_filter_match.restype = C.c_int
+        so.fqz5_filter_match.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                         C.c_uint64, C.c_int, C.c_int, C.c_void_p,
+                                         C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p]
+        so.fqz5_filter_host.restype = C.c_int
+        so.fqz5_filter_host.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_void_p,
+                                        C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]
         _bound = True
     return so
 
@@ -177,7 +195,11 @@ def _load():
 # same with seqs, the sequence sections decoded, in place of names, after
 # table, the patterns expanded and their table built, and before result, the
 # hits mapped back to the caller's patterns; stats: index, read, upload,
-# decode, stats, the histogram kernels, and result, the tables' download);
+# decode, stats, the histogram kernels, and result, the tables' download;
+# filter_records / filter_file: index, read, upload, keys (the blocks parsed
+# and CRC-checked, their key sections decoded; parse where the criteria need no
+# section), filter (the sums and pick kernels), decode, format, download,
+# write);
 # the stages end with what the library synchronises
 _TRACE = {}
 
@@ -2191,18 +2213,22 @@ class _NameTable(_Native):
         return int(self.so.fqz5_names_table_find(self.p, key, len(key)))
 
 
-def _key_windows(rd, key: int, match, pairs: bool, extract: bool, plus_name: bool,
-                 with_qual: bool, device: str, window_bytes: int | None):
+def _key_windows(rd, keys: tuple, stages: tuple, match, pairs: bool, extract: bool,
+                 plus_name: bool, with_qual: bool, device: str, window_bytes: int | None):
     """One pass over the container behind `rd` (see above), window by window,
-    for a lookup whose key is the section `key` (SEC_NAME: by read name,
-    SEC_SEQ: by sequence content): every block is read, checked and
-    CRC-checked and its key section decoded; match(key pointer, its size, the
-    block's record lengths, hits) leaves the block's compacted hits (record
-    indices, query indices) in the device tensor `hits` and returns their
-    number; the other sections are decoded for the blocks with hits alone.
-    Yields (file record numbers of the window's hits, their query indices, the
-    hits' text as device tensors or None without `extract`; pairs: R1 and R2
-    text)."""
+    for a lookup whose keys are the sections `keys` ((SEC_NAME,): by read
+    name, (SEC_SEQ,): by sequence content, the filter by read metrics: none,
+    (SEC_SEQ,) or (SEC_SEQ, SEC_QUAL), a quality section after the bases its
+    decoder reads): every block is read, checked and CRC-checked and the key
+    sections of the window's blocks decoded in one call (none without keys);
+    match(the block's device addresses by section, its BlockView, its record
+    lengths, hits) leaves the block's compacted hits (record indices, query
+    indices) in the device tensor `hits` and returns their number; the other
+    sections are decoded for the blocks with hits alone.  A block without
+    qualities under a SEC_QUAL key is an error that names it.  stages: the
+    trace's names of the key stage and the match stage.  Yields (file record
+    numbers of the window's hits, their query indices, the hits' text as
+    device tensors or None without `extract`; pairs: R1 and R2 text)."""
     import functools
     import torch
     so = _load()
@@ -2212,25 +2238,30 @@ def _key_windows(rd, key: int, match, pairs: bool, extract: bool, plus_name: boo
     for _, _, n in index:
         rec0.append(rec0[-1] + int(n))            # (Python ints: more than 2^32 records)
     for win in _index_windows(rd, index, device, window_bytes):
-        with _stage("names" if key == S.SEC_NAME else "seqs"):
+        with _stage(stages[0] if keys else "parse"):
             win.parse()
             views, lens, fasta = win.views, win.lens, win.fasta
-            kulen = [win.field(j, key)[2] for j in range(len(views))]
+            if S.SEC_QUAL in keys and any(fasta):
+                raise _lib.NativeError(f"block {win.blocks[fasta.index(True)]} has no qualities "
+                                       "for a quality criterion")
+            kulen = [win.field(j, sec)[2] for j in range(len(views)) for sec in keys]
             koff = np.concatenate([[0], np.cumsum(kulen)]).astype(np.int64)
             key_d = torch.empty(int(koff[-1]) + 1, dtype=torch.uint8, device=device)
-            ptr = [{key: key_d.data_ptr() + int(koff[j])} for j in range(len(views))]
+            ptr = [{sec: key_d.data_ptr() + int(koff[j * len(keys) + i])
+                    for i, sec in enumerate(keys)} for j in range(len(views))]
 
             def section(j, sec):          # (the quality decoder reads the block's decoded bases)
                 return win.section(j, sec, ptr[j][sec],
                                    ptr[j][S.SEC_SEQ] if sec == S.SEC_QUAL else None)
-            win.decode([section(j, key) for j in range(len(views))])
+            if keys:
+                win.decode([section(j, sec) for j in range(len(views)) for sec in keys])
         recs, qidx, sels = [], [], {}
-        with _stage("match"):
+        with _stage(stages[1]):
             hits = torch.empty((2, max(max(len(ln) for ln in lens), 1)), dtype=torch.int32,
                                device=device)
             for j, ln in enumerate(lens):
                 _lib.after_torch(device)          # (the last block's hits have been copied)
-                n = match(ptr[j][key], kulen[j], ln, hits)
+                n = match(ptr[j], views[j], ln, hits)
                 if not n:
                     continue
                 got = hits[:, :n].cpu().numpy().view(np.uint32)      # the compacted hits alone
@@ -2248,7 +2279,7 @@ def _key_windows(rd, key: int, match, pairs: bool, extract: bool, plus_name: boo
             rest, o = [], 0
             for j in sels:
                 for sec in (S.SEC_NAME, S.SEC_SEQ, S.SEC_QUAL):
-                    if sec == key or (sec == S.SEC_QUAL and (fasta[j] or not with_qual)):
+                    if sec in keys or (sec == S.SEC_QUAL and (fasta[j] or not with_qual)):
                         continue
                     rest.append((j, sec, o))
                     o += win.field(j, sec)[2]
@@ -2262,7 +2293,7 @@ def _key_windows(rd, key: int, match, pairs: bool, extract: bool, plus_name: boo
                 size, s1 = C.c_uint64(0), C.c_uint64(0)
                 _check(so.fqz5_fastq_format_list(
                     ptr[j][S.SEC_NAME], views[j].name_ulen, ptr[j][S.SEC_SEQ],
-                    ptr[j].get(S.SEC_QUAL), lens[j].ctypes.data,
+                    ptr[j].get(S.SEC_QUAL) if with_qual else None, lens[j].ctypes.data,
                     len(lens[j]), sels[j].data_ptr(), int(sels[j].numel()), int(plus_name),
                     int(pairs), out, cap, C.byref(size), C.byref(s1)), "fqz5_fastq_format_list")
                 return int(size.value), int(s1.value)
@@ -2272,14 +2303,15 @@ def _key_windows(rd, key: int, match, pairs: bool, extract: bool, plus_name: boo
         del key_d, out_d, texts
 
 
-def _lookup(rd, key: int, match, pairs, extract, plus_name, with_qual, device, window_bytes, sink):
+def _lookup(rd, keys: tuple, stages: tuple, match, pairs, extract, plus_name, with_qual, device,
+            window_bytes, sink):
     """_key_windows run to its end: (the hits' file record numbers, their
     query indices, the bytes sink(windows of texts) wrote with `extract`)."""
     recs, qidx = [], []
 
     def windows():
-        for r, q, texts in _key_windows(rd, key, match, pairs, extract, plus_name, with_qual,
-                                        device, window_bytes):
+        for r, q, texts in _key_windows(rd, keys, stages, match, pairs, extract, plus_name,
+                                        with_qual, device, window_bytes):
             recs.append(r)
             qidx.append(q)
             yield texts
@@ -2300,14 +2332,15 @@ def _find(rd, names, whole, pairs, extract, plus_name, with_qual, device, window
         return _name_hits(given, first, [], [], sink(iter(())) if extract else 0)
     so = _load()
     with _NameTable(qs) as tab:
-        def match(d_key, ulen, ln, hits):
+        def match(ptr, v, ln, hits):
             n = C.c_uint64(0)
-            _check(so.fqz5_names_match(tab.p, d_key, ulen, len(ln), int(whole), int(pairs),
-                                       hits[0].data_ptr(), hits[1].data_ptr(), C.byref(n)),
+            _check(so.fqz5_names_match(tab.p, ptr[S.SEC_NAME], v.name_ulen, len(ln), int(whole),
+                                       int(pairs), hits[0].data_ptr(), hits[1].data_ptr(),
+                                       C.byref(n)),
                    "fqz5_names_match")
             return int(n.value)
-        recs, qidx, written = _lookup(rd, S.SEC_NAME, match, pairs, extract, plus_name, with_qual,
-                                      device, window_bytes, sink)
+        recs, qidx, written = _lookup(rd, (S.SEC_NAME,), ("names", "match"), match, pairs, extract,
+                                      plus_name, with_qual, device, window_bytes, sink)
     return _name_hits(given, first, recs, qidx, written)
 
 
@@ -2508,14 +2541,14 @@ def _find_seqs(rd, patterns, revcomp, pairs, extract, plus_name, with_qual, devi
     with tab:
         seen = torch.zeros(len(qs), dtype=torch.uint8, device=device)
 
-        def match(d_key, ulen, ln, hits):
+        def match(ptr, v, ln, hits):
             n = C.c_uint64(0)
-            _check(so.fqz5_seqs_match(tab.p, d_key, ulen, ln.ctypes.data, len(ln), int(pairs),
-                                      hits[0].data_ptr(), hits[1].data_ptr(), C.byref(n),
-                                      seen.data_ptr()), "fqz5_seqs_match")
+            _check(so.fqz5_seqs_match(tab.p, ptr[S.SEC_SEQ], v.seq_ulen, ln.ctypes.data, len(ln),
+                                      int(pairs), hits[0].data_ptr(), hits[1].data_ptr(),
+                                      C.byref(n), seen.data_ptr()), "fqz5_seqs_match")
             return int(n.value)
-        recs, qidx, written = _lookup(rd, S.SEC_SEQ, match, pairs, extract, plus_name, with_qual,
-                                      device, window_bytes, sink)
+        recs, qidx, written = _lookup(rd, (S.SEC_SEQ,), ("seqs", "match"), match, pairs, extract,
+                                      plus_name, with_qual, device, window_bytes, sink)
         seen = seen.cpu().numpy()
     with _stage("result"):
         return _seq_hits(given, qs, origin, revcomp, recs, qidx, seen, written)
@@ -2584,8 +2617,7 @@ def extract_seqs_file(src: str, dst: str, patterns, revcomp: bool = False, plus_
 # into one device accumulator, which comes back once at the end.  The length
 # distribution is built here from the lengths the block headers give and kept
 # sparse.  One process.  Not built: several ranks, per-tile or flowcell
-# statistics from the names, k-mer or duplication levels, adapter content,
-# filtering records by these metrics.
+# statistics from the names, k-mer or duplication levels, adapter content.
 # ---------------------------------------------------------------------------
 STATS_CYCLES_MAX = 1 << 16
 
@@ -2766,3 +2798,207 @@ def stats(src, cycles: int = 1024, pairs: bool = False, per_record: bool = False
         raise ValueError(f"stats: cycles {cycles} not in 1..{STATS_CYCLES_MAX}")
     return _run(_reader(src), "stats", lambda rd: _stats(
         rd, cycles, 2 if pairs else 1, per_record, device, window_bytes))
+
+
+# ---------------------------------------------------------------------------
+# Filter by read metrics
+#
+# "The reads worth keeping": long enough, mean quality high enough, not full
+# of N, not too many low-quality bases, sane GC, not low-complexity (what
+# fastp, seqkit seq -m/-Q and vsearch --fastq_filter do first).  The pass is
+# the lookups' (_key_windows) with a set of key sections the criteria decide:
+# none for length criteria alone (the lengths come from the block headers),
+# SEC_SEQ for a base criterion, SEC_SEQ and SEC_QUAL for a quality criterion
+# (the quality decoder reads the block's bases).  The key sections of a
+# window's blocks are decoded in one call, fqz5_filter_match (filter.hip) sums
+# each block's records and picks on the device, and the remaining sections are
+# decoded in one further call for the blocks with hits alone.  The rule is
+# exact integer arithmetic (include/fqz5_fastq.h); a pair is kept only when
+# both mates pass.  One process.  Not built: trimming or clipping of records,
+# expected-error (maxee) filters, adapter-aware filters, several ranks.
+# ---------------------------------------------------------------------------
+class _FilterSpec(C.Structure):
+    """fqz5_filter_spec (include/fqz5_fastq.h)"""
+    _fields_ = [("set", C.c_uint32), ("min_mean_q", C.c_uint32), ("low_q", C.c_uint32),
+                ("max_low_pct", C.c_uint32), ("gc_min_pct", C.c_uint32), ("gc_max_pct", C.c_uint32),
+                ("min_complexity_pct", C.c_uint32), ("min_len", C.c_uint64),
+                ("max_len", C.c_uint64), ("max_n", C.c_uint64)]
+
+
+class _FilterSums(C.Structure):
+    """fqz5_filter_sums: addresses of n, gc, diff (u32), qsum (u64), lowq (u32)"""
+    _fields_ = [(k, C.c_void_p) for k in ("n", "gc", "diff", "qsum", "lowq")]
+
+
+class Filter:
+    """The criteria of filter_records / filter_file; one left None is off.
+    Integers throughout, the rule exact (include/fqz5_fastq.h): a record of
+    length L passes when
+      min_len, max_len       min_len <= L <= max_len
+      max_n                  its bytes in "Nn" <= max_n
+      min_mean_q             the sum of its qualities >= min_mean_q * L
+      low_q, max_low_pct     100 * (its qualities < low_q) <= max_low_pct * L
+                             (given together)
+      gc_pct = (lo, hi)      lo * L <= 100 * (its bytes in "GCgc") <= hi * L
+      min_complexity_pct     100 * (its positions that differ from their
+                             right-hand neighbour) >= min_complexity_pct *
+                             max(L - 1, 0)
+    A quality is the quality line's byte - 33.  ValueError: a negative value,
+    a percentage over 100, lo > hi, low_q without max_low_pct or the reverse,
+    min_len > max_len."""
+
+    def __init__(self, min_len=None, max_len=None, max_n=None, min_mean_q=None, low_q=None,
+                 max_low_pct=None, gc_pct=None, min_complexity_pct=None):
+        import operator
+        lo, hi = (None, None) if gc_pct is None else gc_pct
+        vals = {"min_len": min_len, "max_len": max_len, "max_n": max_n, "min_mean_q": min_mean_q,
+                "low_q": low_q, "max_low_pct": max_low_pct, "gc_pct lo": lo, "gc_pct hi": hi,
+                "min_complexity_pct": min_complexity_pct}
+        for k, v in vals.items():
+            if v is None:
+                continue
+            vals[k] = v = operator.index(v)
+            if v < 0:
+                raise ValueError(f"Filter: {k} is negative")
+            if (k.endswith("_pct") or k.startswith("gc_pct")) and v > 100:
+                raise ValueError(f"Filter: {k} is a percentage over 100")
+        if gc_pct is not None and (vals["gc_pct lo"] is None or vals["gc_pct hi"] is None):
+            raise ValueError("Filter: gc_pct is (lo, hi)")
+        if gc_pct is not None and vals["gc_pct lo"] > vals["gc_pct hi"]:
+            raise ValueError("Filter: gc_pct has lo > hi")
+        if (low_q is None) != (max_low_pct is None):
+            raise ValueError("Filter: low_q and max_low_pct go together")
+        if min_len is not None and max_len is not None and vals["min_len"] > vals["max_len"]:
+            raise ValueError("Filter: min_len > max_len")
+        self.min_len, self.max_len, self.max_n = vals["min_len"], vals["max_len"], vals["max_n"]
+        self.min_mean_q, self.low_q = vals["min_mean_q"], vals["low_q"]
+        self.max_low_pct, self.min_complexity_pct = vals["max_low_pct"], vals["min_complexity_pct"]
+        self.gc_pct = None if gc_pct is None else (vals["gc_pct lo"], vals["gc_pct hi"])
+
+    def spec(self) -> _FilterSpec:
+        """The criteria as the library takes them (values past a field's range
+        clipped to it: no record is that long, no quality sum that large)."""
+        f = _FilterSpec()
+        u32, u64 = (1 << 32) - 1, (1 << 64) - 1
+        for k, (name, top) in enumerate((("min_len", u64), ("max_len", u64), ("max_n", u64),
+                                         ("min_mean_q", u32), ("low_q", u32), (None, 0),
+                                         ("min_complexity_pct", u32))):
+            v = getattr(self, name) if name else None
+            if v is not None:
+                f.set |= 1 << k
+                setattr(f, name, min(v, top))
+        if self.low_q is not None:
+            f.max_low_pct = self.max_low_pct
+        if self.gc_pct is not None:
+            f.set |= 1 << 5
+            f.gc_min_pct, f.gc_max_pct = self.gc_pct
+        return f
+
+    def keys(self) -> tuple:
+        """The sections the criteria are judged on (see above)."""
+        if self.min_mean_q is not None or self.low_q is not None:
+            return (S.SEC_SEQ, S.SEC_QUAL)
+        if self.max_n is not None or self.gc_pct is not None or self.min_complexity_pct is not None:
+            return (S.SEC_SEQ,)
+        return ()
+
+
+class FilterHits:
+    """The result of a filter: `records` (np.uint64) the file record numbers
+    selected, ascending (pairs: both mates); `total` the units seen (records,
+    with pairs pairs); `failed` (np.uint64[7]) the units that failed, by the
+    lowest criterion they fail in the order of REASONS (with invert these are
+    the units selected); `written` the text bytes written (filter_file)."""
+    REASONS = ("min_len", "max_len", "max_n", "min_mean_q", "low_q", "gc_pct",
+               "min_complexity_pct")
+
+    def __init__(self, records, total: int, failed, written: int = 0):
+        self.records, self.total, self.failed, self.written = records, total, failed, written
+
+
+def _filter_host(flt: Filter, seq, qual, lens, pairs: bool = False, invert: bool = False):
+    """fqz5_filter_host of one block: (keep per record, failed[7], the sums
+    n, gc, diff, qsum, lowq)."""
+    so = _load()
+    lens = np.ascontiguousarray(lens, np.uint32)
+    keep = np.zeros(len(lens), np.uint8)
+    failed = np.zeros(7, np.uint64)
+    sums = [np.zeros(len(lens), np.uint64 if k == 3 else np.uint32) for k in range(5)]
+    spec = flt.spec()
+    _check(so.fqz5_filter_host(C.byref(spec), None if seq is None else bytes(seq),
+                               None if qual is None else bytes(qual),
+                               len(seq) if seq is not None else int(lens.astype(np.uint64).sum()),
+                               lens.ctypes.data, len(lens), int(pairs), int(invert),
+                               keep.ctypes.data, failed.ctypes.data,
+                               C.byref(_FilterSums(*(a.ctypes.data for a in sums)))),
+           "fqz5_filter_host")
+    return keep, failed, sums
+
+
+def _filter(rd, flt: Filter, pairs, invert, extract, plus_name, with_qual, device, window_bytes,
+            sink) -> FilterHits:
+    """The filter over `rd`; sink(windows of texts) consumes the selected
+    records' text (extract) and returns the bytes written."""
+    if not isinstance(flt, Filter):
+        raise TypeError("the criteria are a Filter")
+    so = _load()
+    spec, failed, total = flt.spec(), np.zeros(7, np.uint64), [0]
+
+    def match(ptr, v, ln, hits):
+        n = C.c_uint64(0)
+        _check(so.fqz5_filter_match(C.byref(spec), ptr.get(S.SEC_SEQ), ptr.get(S.SEC_QUAL),
+                                    v.seq_ulen, ln.ctypes.data, len(ln), int(pairs), int(invert),
+                                    hits[0].data_ptr(), C.byref(n), failed.ctypes.data, None),
+               "fqz5_filter_match")
+        total[0] += len(ln) // (2 if pairs else 1)
+        return int(n.value)
+    recs, _, written = _lookup(rd, flt.keys(), ("keys", "filter"), match, pairs, extract, plus_name,
+                               with_qual, device, window_bytes, sink)
+    return FilterHits(np.asarray(recs, np.uint64), total[0], failed, written)
+
+
+def filter_records(src, flt: Filter, pairs: bool = False, invert: bool = False,
+                   device: str = "cuda", window_bytes: int | None = None) -> FilterHits:
+    """The records of a .fqz5 (a path, the file's bytes, or a positioned
+    reader) that pass the criteria `flt`, judged on the GPU (see above): every
+    block is read, checked and CRC-checked; only the sections the criteria
+    need are decoded (none for length criteria alone) and no name section.
+    pairs: records 2k and 2k + 1 are one unit, kept only when both mates pass
+    (a block with an odd record count is an error).  invert: exactly the units
+    that do not pass.  A quality criterion on a block without qualities is an
+    error."""
+    return _run(_reader(src), "filter_records", lambda rd: _filter(
+        rd, flt, pairs, invert, False, False, True, device, window_bytes, None))
+
+
+def filter_bytes(data, flt: Filter, plus_name: bool = False, with_qual: bool = True,
+                 invert: bool = False, device: str = "cuda") -> bytes:
+    """The records of a .fqz5 held in memory that pass `flt`, in file order,
+    as the text decompress_bytes gives for them (with_qual False: FASTA
+    text).  See filter_records."""
+    out = []
+    _filter(_PosBytes(data), flt, False, invert, True, plus_name, with_qual, device, None,
+            _bytes_sink(out))
+    _trace_dump("filter")
+    return b"".join(out)
+
+
+def filter_file(src: str, dst: str, flt: Filter, plus_name: bool = False, device: str = "cuda",
+                dst2: str | None = None, with_qual: bool = True, invert: bool = False,
+                window_bytes: int | None = None) -> FilterHits:
+    """The records of the .fqz5 file src that pass `flt` to dst, in file
+    order: one pass over the file in windows of at most `window_bytes` of
+    compressed data; every block is read once, checked against its index entry
+    and CRC-checked, the sections the criteria need decoded and judged on the
+    GPU; the remaining sections are decoded for the blocks with selected
+    records only, and their text is laid out on the GPU
+    (fqz5_fastq_format_list).  dst2: the records are interleaved pairs, a pair
+    is kept only when both mates pass, R1 records to dst and R2 records to
+    dst2.  with_qual False: the text is FASTA, and no quality section is
+    decoded unless a criterion needs it.  invert: the records that do not
+    pass.  A ".gz" destination is gzip-compressed.  One process; returns the
+    FilterHits (`written`: the text bytes written)."""
+    outs = [dst] + ([dst2] if dst2 is not None else [])
+    return _run((_PosFile(src), True), "filter", lambda rd: _filter(
+        rd, flt, dst2 is not None, invert, True, plus_name, with_qual, device, window_bytes,
+        lambda w: sum(_write_texts(outs, w))))

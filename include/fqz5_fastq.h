@@ -35,6 +35,10 @@
  *   fqz5_stats_*        read QC statistics: a block's decoded bases and
  *                       qualities histogrammed into a device accumulator
  *                       (fqz5file.stats).
+ *   fqz5_filter_*       filter by read metrics: the records of a block whose
+ *                       length, N count, mean quality, low-quality share, GC
+ *                       share and complexity pass a rule, picked on the
+ *                       device (fqz5file.filter_records / filter_file).
  *
  * Offsets are bytes into the text.  Calls return 0 (fqz5_fastq_index: 1 for
  * FASTA text; fqz5_fastq_blocks: the block count) or -1 with
@@ -283,6 +287,75 @@ int fqz5_stats_read(const fqz5_stats *, uint64_t *h_out, uint64_t cap);
 int fqz5_stats_host(uint32_t cycles, int mates, const uint8_t *seq, const uint8_t *qual,
                     uint64_t seq_len, const uint32_t *lens, uint64_t nrec, uint64_t *h_out,
                     uint64_t cap, uint64_t *rec_qsum, uint32_t *rec_gc);
+
+/* Filter by read metrics (filter.hip; fqz5file.filter_records): which records
+ * of a block's decoded bases and qualities are worth keeping.  The rule is
+ * exact integer arithmetic, every product in u64, and the device and
+ * fqz5_filter_host agree bit for bit.  Per record:
+ *     L     its length
+ *     n     its bytes in "Nn"
+ *     gc    its bytes in "GCgc"
+ *     diff  the positions 0 <= i < L - 1 with s[i] != s[i + 1], bytes compared
+ *           as they are; a neighbour in the next record never counts
+ *     qsum  the sum of its q (the quality line's byte - 33, as the decoder
+ *           leaves it)
+ *     lowq  its q below low_q (0 unless criterion 4 is set)
+ * A criterion counts only where its bit (1 << index) is in `set`:
+ *     0 min_len             L >= min_len
+ *     1 max_len             L <= max_len
+ *     2 max_n               n <= max_n
+ *     3 min_mean_q          qsum >= min_mean_q * L
+ *     4 low_q, max_low_pct  100 * lowq <= max_low_pct * L
+ *     5 gc_min_pct, gc_max_pct
+ *                           gc_min_pct * L <= 100 * gc <= gc_max_pct * L
+ *     6 min_complexity_pct  100 * diff >= min_complexity_pct * max(L - 1, 0)
+ * so with L = 0 criteria 2..6 hold and the lengths alone decide.  A record
+ * passes when it passes every criterion that is set; its reason is the lowest
+ * index it fails.  A unit is one record, with pairs the records 2k and 2k + 1:
+ * a pair passes only when both mates pass (the lookups take a pair on either
+ * mate), and its reason is the lowest index either mate fails.  The selected
+ * units are those that pass, with invert exactly those that do not. */
+#define FQZ5_FILTER_REASONS 7
+typedef struct {
+    uint32_t set;                 /* bit k: criterion k counts */
+    uint32_t min_mean_q, low_q, max_low_pct, gc_min_pct, gc_max_pct, min_complexity_pct;
+    uint64_t min_len, max_len, max_n;
+} fqz5_filter_spec;
+
+/* per record (nrec entries each; any may be NULL): the sums above */
+typedef struct {
+    uint32_t *n, *gc, *diff;
+    uint64_t *qsum;
+    uint32_t *lowq;
+} fqz5_filter_sums;
+
+/* bases per tile of the sums kernel */
+uint32_t fqz5_filter_tile(void);
+
+/* d_seq[0..seq_len) and d_qual[0..seq_len) (device) hold nrec records whose
+ * lengths are h_len (host).  The selected records' indices go, ascending,
+ * into d_rec (device, nrec entries; both mates of a selected pair), *n_hit
+ * their number; h_failed[reason] (host, 7 words, added to) counts the units
+ * that failed, whether or not invert selects them.  The bases are streamed
+ * only when one of criteria 2, 5, 6 is set or d_sums is given, the qualities
+ * only when 3 or 4 is set or d_sums is given; a stream that is not needed may
+ * be NULL (both with length criteria alone: no sums kernel runs), and one that
+ * is NULL leaves its sums 0.  d_sums (may be NULL): device arrays that
+ * receive the per-record sums.  Fails, before anything is written: criterion
+ * 2, 5 or 6 with d_seq NULL, criterion 3 or 4 with d_qual NULL, lengths that
+ * do not sum to seq_len, nrec >= 2^31, an odd nrec with pairs. */
+int fqz5_filter_match(const fqz5_filter_spec *, const uint8_t *d_seq, const uint8_t *d_qual,
+                      uint64_t seq_len, const uint32_t *h_len, uint64_t nrec, int pairs,
+                      int invert, uint32_t *d_rec, uint64_t *n_hit, uint64_t *h_failed,
+                      const fqz5_filter_sums *d_sums);
+
+/* Host restatement of the rule, one thread, no GPU: keep[r] (nrec bytes) = 1
+ * where record r is selected, failed as above, sums (host arrays, may be
+ * NULL) as above.  Every stream given is summed.  Fails as fqz5_filter_match
+ * does. */
+int fqz5_filter_host(const fqz5_filter_spec *, const uint8_t *seq, const uint8_t *qual,
+                     uint64_t seq_len, const uint32_t *lens, uint64_t nrec, int pairs, int invert,
+                     uint8_t *keep, uint64_t *failed, const fqz5_filter_sums *sums);
 
 #ifdef __cplusplus
 }
