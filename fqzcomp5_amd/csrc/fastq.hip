@@ -41,6 +41,12 @@ constexpr int FQ_TPB = 256;
 constexpr uint32_t FQ_STEP = FQ_TPB * 16;          // bytes per workgroup iteration
 constexpr uint32_t FQ_ITERS = 16;
 constexpr uint64_t FQ_TILE = uint64_t(FQ_STEP) * FQ_ITERS;   // 64 KiB
+// a parse kernel's status word: the first (lowest) record or line that is not
+// what the kernel parses, FQ_ALL_OK when there is none
+constexpr int32_t FQ_ALL_OK = 0x7fffffff;
+__device__ __forceinline__ void first_bad(int32_t *status, uint64_t i) {
+    atomicMin(status, int32_t(i < 0x7ffffffeull ? i : 0x7ffffffeull));
+}
 
 __device__ __forceinline__ uint32_t count_in16(const uint8_t *t, uint64_t at, uint64_t len,
                                                uint8_t ch) {
@@ -116,7 +122,7 @@ __device__ __forceinline__ void header(const uint8_t *t, uint64_t s0, uint64_t e
 }
 
 // record r = lines 4r..4r+3 (kseq_read, kseq.h:178-218)
-__global__ void k_fq_records(const uint8_t *t, const uint64_t *nl, uint64_t nrec,
+__global__ void k_fq_records(const uint8_t *t, uint64_t len, const uint64_t *nl, uint64_t nrec,
                              fqz5_fastq_rec *recs, uint32_t *rec_size, int32_t *status) {
     const uint64_t r = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (r >= nrec) return;
@@ -134,26 +140,33 @@ __global__ void k_fq_records(const uint8_t *t, const uint64_t *nl, uint64_t nrec
     R.seq_len = uint32_t(strip_cr(t, s1, e1) - s1);
     R.qual = s3;
     R.fasta = 0;
-    R.end = e3 + 1;
+    R.end = e3 + 1 < len ? e3 + 1 : len;              // (a last line without '\n' ends at len)
     const uint32_t ql = uint32_t(strip_cr(t, s3, e3) - s3);
     if (ql != R.seq_len) bad = 1;                     // kseq -2 (:213-216)
     recs[r] = R;
     rec_size[r] = R.name_len + 1 + 2 * R.seq_len;     // load_seqs_kseq's record_size (:472)
-    if (bad) atomicMin(status, int32_t(-1 - int32_t(r < 0x7ffffffeull ? r : 0x7ffffffeull)));
+    if (bad) first_bad(status, r);
 }
 
-// FASTA lines: a header starts with '>'; a line starting with '@' or '+'
-// would make kseq read a FASTQ record (kseq.h:194, :206) and is refused, as
-// is text whose first line is not a header
-__global__ void k_fa_lines(const uint8_t *t, const uint64_t *nl, uint64_t nlines, uint32_t *hdr,
-                           int32_t *status) {
+// the text end for FASTA records: a bare '>' as the last line (nothing after
+// it, not even '\n') starts no record, kseq's name read returns -1 at the
+// end of the file (kseq.h:188, :137), so the records end before it
+__device__ __forceinline__ uint64_t fa_text_end(const uint8_t *t, uint64_t len) {
+    return len && t[len - 1] == '>' && (len == 1 || t[len - 2] == '\n') ? len - 1 : len;
+}
+
+// FASTA lines: a header starts with '>' (but a bare '>' that ends the text is
+// none, fa_text_end); a line starting with '@' or '+' would make kseq read a
+// FASTQ record (kseq.h:194, :206) and is refused, as is text whose first line
+// is not a header
+__global__ void k_fa_lines(const uint8_t *t, uint64_t len, const uint64_t *nl, uint64_t nlines,
+                           uint32_t *hdr, int32_t *status) {
     const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= nlines) return;
     const uint64_t s = i ? nl[i - 1] + 1 : 0, e = nl[i];
     const uint8_t c = e > s ? t[s] : uint8_t('\n');
-    hdr[i] = c == '>';
-    if (c == '@' || c == '+' || (i == 0 && c != '>'))
-        atomicMin(status, int32_t(-1 - int32_t(i < 0x7ffffffeull ? i : 0x7ffffffeull)));
+    hdr[i] = c == '>' && s < fa_text_end(t, len);
+    if (c == '@' || c == '+' || (i == 0 && c != '>')) first_bad(status, i);
 }
 
 __global__ void k_fa_scatter(const uint32_t *hdr, const uint32_t *pos, uint64_t nlines, uint64_t *hl) {
@@ -164,8 +177,11 @@ __global__ void k_fa_scatter(const uint32_t *hdr, const uint32_t *pos, uint64_t 
 // kseq's FASTA sequence over text [sb, se) (kseq.h:194-198): every line's
 // bytes joined, empty lines skipped, a '\r' before a line end dropped unless
 // it would be the sequence's only byte (the KS_SEP_LINE strip, :141, tests
-// the whole sequence's length).  One wave: returns the byte count and, with
-// `out`, writes the bytes.
+// the whole sequence's length).  A line the text end cuts off (se reached
+// without a '\n') is stripped the same way, X '\r' gives X, except a '\r'
+// alone on that line: ks_getc appends it and the line read after it returns
+// -1 at the end of the file before the strip (:137), so it is kept.  One
+// wave: returns the byte count and, with `out`, writes the bytes.
 __device__ uint32_t fa_seq(const uint8_t *t, uint64_t sb, uint64_t se, uint8_t *out) {
     const uint32_t lane = threadIdx.x & 63;
     uint32_t n = 0;
@@ -177,7 +193,9 @@ __device__ uint32_t fa_seq(const uint8_t *t, uint64_t sb, uint64_t se, uint8_t *
         const uint64_t below = (lane ? (~0ull >> (64 - lane)) : 0ull);
         const bool before = any || (nonl & below) != 0;
         bool keep = c != '\n';
-        if (c == '\r' && (p + 1 == se || t[p + 1] == '\n') && before) keep = false;
+        if (c == '\r' && before) {                    // (p < se: no byte past se is read)
+            if (p + 1 == se ? !(p == sb || t[p - 1] == '\n') : t[p + 1] == '\n') keep = false;
+        }
         const uint64_t km = __builtin_amdgcn_ballot_w64(keep);
         if (keep && out) out[n + __builtin_popcountll(km & below)] = c;
         n += uint32_t(__builtin_popcountll(km));
@@ -187,15 +205,16 @@ __device__ uint32_t fa_seq(const uint8_t *t, uint64_t sb, uint64_t se, uint8_t *
 }
 
 // one wave per FASTA record: header line hl[r], its sequence up to the next
-// header (or the text end); R.qual holds that end offset
+// header (or the text end, fa_text_end); R.qual holds that end offset
 __global__ void k_fa_records(const uint8_t *t, uint64_t len, const uint64_t *nl, const uint64_t *hl,
                              uint64_t nrec, fqz5_fastq_rec *recs, uint32_t *rec_size) {
     const uint64_t r = (uint64_t(blockIdx.x) * blockDim.x + threadIdx.x) / 64;
     if (r >= nrec) return;
     const uint64_t h = hl[r];
     const uint64_t s0 = h ? nl[h - 1] + 1 : 0, e0 = nl[h];
-    const uint64_t sb = e0 + 1 < len ? e0 + 1 : len;
-    const uint64_t se = r + 1 < nrec ? nl[hl[r + 1] - 1] + 1 : len;
+    const uint64_t tend = fa_text_end(t, len);
+    const uint64_t sb = e0 + 1 < tend ? e0 + 1 : tend;
+    const uint64_t se = r + 1 < nrec ? nl[hl[r + 1] - 1] + 1 : tend;
     const uint32_t n = fa_seq(t, sb, se, nullptr);
     if ((threadIdx.x & 63) == 0) {
         fqz5_fastq_rec R;
@@ -724,7 +743,7 @@ uint64_t *text_lines(GpuCtx &g, const uint8_t *d_text, uint64_t len, bool eof, u
 // 4-line FASTQ check of the complete groups of lines: records into d_recs
 // (scratch when NULL); true when every group is a 4-line record and (eof)
 // the lines after them are empty
-bool four_line(GpuCtx &g, const uint8_t *d_text, const uint64_t *lines, uint64_t nlines, bool eof,
+bool four_line(GpuCtx &g, const uint8_t *d_text, uint64_t len, const uint64_t *lines, uint64_t nlines, bool eof,
                fqz5_fastq_rec *d_recs, uint32_t *rs, uint64_t *n4out) {
     const uint64_t n4 = nlines / 4;
     *n4out = n4;
@@ -744,13 +763,13 @@ bool four_line(GpuCtx &g, const uint8_t *d_text, const uint64_t *lines, uint64_t
     if (!d_recs) d_recs = g.arena.alloc_n<fqz5_fastq_rec>(size_t(n4));
     if (!rs) rs = g.arena.alloc_n<uint32_t>(size_t(n4));
     int32_t *st = g.arena.alloc_n<int32_t>(1);
-    g.memset0(st, 4);
-    hipLaunchKernelGGL(k_fq_records, grid_for(n4, 256), dim3(256), 0, g.stream, d_text, lines, n4, d_recs, rs, st);
+    FQZ5_HIP(hipMemcpyAsync(st, &FQ_ALL_OK, 4, hipMemcpyHostToDevice, g.stream));
+    hipLaunchKernelGGL(k_fq_records, grid_for(n4, 256), dim3(256), 0, g.stream, d_text, len, lines, n4, d_recs, rs, st);
     FQZ5_HIP(hipGetLastError());
     int32_t status = 0;
     g.download(&status, st, 1);
     g.sync();
-    return status >= 0;
+    return status == FQ_ALL_OK;
 }
 
 }  // namespace
@@ -799,8 +818,7 @@ int fqz5_fastq_index(const uint8_t *d_text, uint64_t len, fqz5_fastq_rec *d_recs
             nlines = nn + 1;
         }
         int32_t *st = g.arena.alloc_n<int32_t>(1);
-        const int32_t ok = 0;
-        FQZ5_HIP(hipMemcpyAsync(st, &ok, 4, hipMemcpyHostToDevice, g.stream));
+        FQZ5_HIP(hipMemcpyAsync(st, &FQ_ALL_OK, 4, hipMemcpyHostToDevice, g.stream));
         uint64_t n4 = 0;
         uint32_t *rs = nullptr;
         if (fasta) {
@@ -809,8 +827,8 @@ int fqz5_fastq_index(const uint8_t *d_text, uint64_t len, fqz5_fastq_rec *d_recs
             uint32_t *pos = g.arena.alloc_n<uint32_t>(size_t(nlines) + 1);
             if (nlines >= (1ull << 31)) throw GpuError("fasta: too many lines");
             if (nlines)
-                hipLaunchKernelGGL(k_fa_lines, grid_for(nlines, 256), dim3(256), 0, g.stream, d_text, lines,
-                                   nlines, hdr, st);
+                hipLaunchKernelGGL(k_fa_lines, grid_for(nlines, 256), dim3(256), 0, g.stream, d_text, len,
+                                   lines, nlines, hdr, st);
             g.memset0(hdr + nlines, 4);
             excl_sum(g, hdr, pos, nlines + 1);
             uint32_t nh = 0;
@@ -844,7 +862,7 @@ int fqz5_fastq_index(const uint8_t *d_text, uint64_t len, fqz5_fastq_rec *d_recs
             if (n4 > max_rec) throw GpuError("fastq: more records than max_rec");
             rs = g.arena.alloc_n<uint32_t>(size_t(n4) + 1);
             if (n4)
-                hipLaunchKernelGGL(k_fq_records, grid_for(n4, 256), dim3(256), 0, g.stream, d_text, lines,
+                hipLaunchKernelGGL(k_fq_records, grid_for(n4, 256), dim3(256), 0, g.stream, d_text, len, lines,
                                    n4, d_recs, rs, st);
         }
         FQZ5_HIP(hipGetLastError());
@@ -852,11 +870,11 @@ int fqz5_fastq_index(const uint8_t *d_text, uint64_t len, fqz5_fastq_rec *d_recs
         g.download(&status, st, 1);
         if (h_rec_size && n4) g.download(h_rec_size, rs, n4);
         g.sync();
-        if (status < 0) {
+        if (status != FQ_ALL_OK) {
             char msg[128];
             std::snprintf(msg, sizeof msg, fasta ? "fasta: line %lld starts a FASTQ record or precedes the first header"
                                                  : "fastq: record %lld is not a 4-line FASTQ record",
-                          static_cast<long long>(-1 - int64_t(status)));
+                          static_cast<long long>(status));
             throw GpuError(msg);
         }
         *nrec = n4;
@@ -907,7 +925,7 @@ int fqz5_fastq_record_ends(const uint8_t *d_text, uint64_t len, int eof, uint64_
         const uint64_t *lines = text_lines(g, d_text, len, eof != 0, &nlines);
         std::vector<uint64_t> ends;
         uint64_t n4 = 0;
-        if (four_line(g, d_text, lines, nlines, eof != 0, nullptr, nullptr, &n4)) {
+        if (four_line(g, d_text, len, lines, nlines, eof != 0, nullptr, nullptr, &n4)) {
             // record r ends after line 4r + 3 (load_seqs_kseq's 4-line records)
             ends.resize(size_t(n4));
             if (n4) {

@@ -10,7 +10,8 @@
  *                       first byte is '>' is FASTA: a record per header
  *                       line, its sequence lines joined as kseq joins them
  *                       (kseq.h:194-198; no quality section in its blocks,
- *                       fqzcomp5.c:575-578, :2258-2264).  Other text fails
+ *                       fqzcomp5.c:575-578, :2258-2264); a bare '>' as the
+ *                       last line is no record.  Other text fails
  *                       (multi-line FASTQ); it is never parsed on the host.
  *   fqz5_fastq_blocks   the block split rule (fqzcomp5.c:471-479): a record
  *                       that would take a non-empty block past blk_size
@@ -60,11 +61,16 @@ typedef struct {                  /* one record of the text */
                                                  in [seq, qual); 2: wrapped
                                                  FASTQ, sequence and quality
                                                  lines from seq and qual */
-    uint64_t end;                             /* the record's text end */
+    uint64_t end;                             /* the offset after the record's
+                                                 last line ('\n' included), never
+                                                 above len; FASTA: the next
+                                                 header's offset (a bare '>' that
+                                                 ends the text included) or len */
 } fqz5_fastq_rec;
 
 /* Index the records of d_text[0..len) (device) into d_recs (device, max_rec
- * entries; len / 6 + 1 always suffice); *nrec receives their number and
+ * entries; len / 6 + 1 always suffice for 4-line FASTQ, the number of lines
+ * for FASTA, whose shortest record is ">\n"); *nrec receives their number and
  * h_rec_size (host, max_rec entries, may be NULL) each record's
  * load_seqs_kseq size. */
 int fqz5_fastq_index(const uint8_t *d_text, uint64_t len, fqz5_fastq_rec *d_recs,
