@@ -16,6 +16,7 @@
 #include <chrono>
 
 #include "../../include/fqz5_mi355x.h"
+#include "kernels.h"
 #include "rans_codec.hpp"
 #include "rans_format.hpp"
 #include "fqz_kernels.h"
@@ -785,6 +786,34 @@ void fqz5_profile_read(double *out6) {
     } catch (const std::exception &e) {
         g_err = e.what();
     }
+}
+
+// One thread's walk of k_unrle_expand on the host, with the kernel's own run
+// arithmetic (kernels.h unrle_*): nlit literals, all of them RLE symbols,
+// from output offset o, their runs the terminator-delimited varints of
+// runs[0..nrun).  out3: the saturated end offset (> nout: refused), the trips
+// of the write loop, the longest single fill.  No device is used.
+int fqz5_unrle_selftest(const unsigned char *runs, unsigned nrun, unsigned nlit, unsigned nout,
+                        unsigned o, uint64_t *out3) {
+    if (nout == UINT32_MAX) return -1;
+    uint64_t trips = 0, longest = 0;
+    uint32_t s = 0;
+    for (unsigned i = 0; i < nlit; i++) {
+        uint32_t e = s;
+        while (e < nrun && (runs[e] & 0x80)) e++;
+        uint32_t r = 0;
+        if (s < nrun) r = unrle_varint(runs, s, e < nrun ? e : nrun - 1);
+        s = e < nrun ? e + 1 : nrun;
+        const uint32_t span = unrle_span(r, nout), fill = unrle_fill(o, span, nout);
+        if (fill && uint64_t(o) + fill > nout) return -1;
+        trips += fill;
+        longest = std::max<uint64_t>(longest, fill);
+        o = unrle_add(o, span, nout);
+    }
+    out3[0] = o;
+    out3[1] = trips;
+    out3[2] = longest;
+    return 0;
 }
 
 long fqz5_fqz_div_selftest(void) {

@@ -19,6 +19,7 @@
 // slot - start = 0, or = slot in the split layout.
 #include "host_rans.hpp"
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
@@ -27,13 +28,20 @@
 namespace fqz5 {
 namespace host {
 
-bool rans_parse_o0(const uint8_t *p, const uint8_t *end, std::vector<uint32_t> &Fv, uint32_t *used) {
+bool rans_parse_o0(const uint8_t *p, const uint8_t *end, std::vector<uint32_t> &Fv, uint32_t *used,
+                   bool skip) {
     uint32_t F[256] = {0}, tot = 0;
     const int k = get_freq0(p, end, F, &tot);
     if (!k) return false;
     scale_pow2(F, tot, 4096);
     uint32_t x = 0;
-    for (int s = 0; s < 256; s++) x += F[s];
+    for (int s = 0; s < 256; s++) {
+        // skip: a frequency larger than the slots left is passed over, as the
+        // 32-state decoder's table builder does (rans_F_to_s3,
+        // rANS_static16_int.h:540); the 4-state decoder refuses the table
+        if (skip && F[s] > 4096 - std::min(x, 4096u)) F[s] = 0;
+        x += F[s];
+    }
     if (x != 4096) return false;
     Fv.assign(F, F + 256);
     *used = uint32_t(k);
@@ -297,6 +305,103 @@ int rans_dec_stream(const uint8_t *in, size_t in_size, uint8_t *out, size_t out_
         return -1;
     *out_size = osz;
     return 0;
+}
+
+// ---- a stream that runs out of words, as the reference decodes it -----------
+// (rANS_static4x16pr.c:335-340, :740-790; rANS_static32x16pr.c:360-400)
+
+namespace {
+
+// slot -> symbol, and each symbol's frequency and first slot; zeroed for a
+// context without frequencies
+struct RefRow {
+    std::vector<uint8_t> sym;
+    uint16_t f[256] = {0}, b[256] = {0};
+};
+
+void ref_row(const uint32_t *F, int bits, RefRow &t) {
+    t.sym.assign(size_t(1) << bits, 0);
+    uint32_t x = 0;
+    for (int s = 0; s < 256; s++) {
+        if (!F[s] || F[s] > (1u << bits) - x) continue;
+        t.f[s] = uint16_t(F[s]);
+        t.b[s] = uint16_t(x);
+        std::memset(&t.sym[x], s, F[s]);
+        x += F[s];
+    }
+}
+
+inline uint32_t ref_renorm(uint32_t x, const uint8_t *&p, const uint8_t *end) {
+    if (x < LOW && p + 1 < end) {
+        x = (x << 16) | p[0] | uint32_t(p[1]) << 8;
+        p += 2;
+    }
+    return x;
+}
+
+inline uint32_t ref_step(uint32_t &x, const RefRow &t, int bits, const uint8_t *&p,
+                         const uint8_t *end) {
+    const uint32_t m = x & ((1u << bits) - 1), s = t.sym[m];
+    x = ref_renorm(t.f[s] * (x >> bits) + m - t.b[s], p, end);
+    return s;
+}
+
+}  // namespace
+
+bool rans_dec_ref(const uint8_t *in, uint32_t len, uint8_t *out, uint32_t n, bool o1, int nx) {
+    if (nx != 4 && nx != 32) return false;
+    if (len < (o1 && nx == 32 ? 128u : 16u)) return false;
+    const uint8_t *end = in + len, *cp = in;
+    std::vector<uint32_t> F;
+    std::vector<uint8_t> alpha(1, 0);
+    int bits = 12;
+    uint32_t used = 0;
+    if (!o1) {
+        if (!rans_parse_o0(in, end, F, &used, nx == 32)) return false;
+        cp = in + used;
+    } else {
+        bits = in[0] >> 4;
+        if (bits != 10 && bits != 12) return false;
+        if (in[0] & 1) {
+            uint32_t u, c, q = 1;
+            q += varint_get(in + q, end, &u);
+            q += varint_get(in + q, end, &c);
+            if (c > len - q || u > (1u << 24)) return false;
+            std::vector<uint8_t> hdr(u);
+            if (!rans_dec_ref(in + q, c, hdr.data(), u, false, 4)) return false;
+            if (!rans_parse_o1(hdr.data(), hdr.data() + u, bits, F, alpha, &used)) return false;
+            cp = in + q + c;
+        } else {
+            if (!rans_parse_o1(in + 1, end, bits, F, alpha, &used)) return false;
+            cp = in + 1 + used;
+        }
+    }
+    if (end - cp < 4 * nx) return false;
+    uint32_t R[32];
+    for (int z = 0; z < nx; z++, cp += 4) {
+        R[z] = rd32(cp);
+        if (R[z] < LOW) return false;
+    }
+    std::vector<RefRow> rows(alpha.size() + 1);      // the last: a context without a row
+    int rowof[256];
+    std::fill(rowof, rowof + 256, int(alpha.size()));
+    for (size_t r = 0; r < alpha.size(); r++) {
+        ref_row(&F[r * 256], bits, rows[r]);
+        rowof[alpha[r]] = int(r);
+    }
+    rows.back().sym.assign(size_t(1) << bits, 0);
+    if (!o1) {
+        for (uint32_t i = 0; i < n; i++) out[i] = uint8_t(ref_step(R[i % nx], rows[0], bits, cp, end));
+        return true;
+    }
+    const uint32_t isz = n / uint32_t(nx);
+    uint8_t L[32] = {0};
+    for (uint32_t k = 0; k < isz; k++)
+        for (int z = 0; z < nx; z++)
+            out[z * isz + k] = L[z] = uint8_t(ref_step(R[z], rows[rowof[L[z]]], bits, cp, end));
+    for (uint32_t p = nx * isz; p < n; p++)
+        out[p] = L[nx - 1] = uint8_t(ref_step(R[nx - 1], rows[rowof[L[nx - 1]]], bits, cp, end));
+    return true;
 }
 
 // ---- the encoder's bare chains (rans_chain.hip chain_body_2w) ---------------

@@ -25,7 +25,8 @@ namespace host {
 // occurs.
 // decode_freq + normalise_freq_shift of an order-0 table at [p, end):
 // *used = its bytes.
-bool rans_parse_o0(const uint8_t *p, const uint8_t *end, std::vector<uint32_t> &F, uint32_t *used);
+bool rans_parse_o0(const uint8_t *p, const uint8_t *end, std::vector<uint32_t> &F, uint32_t *used,
+                   bool skip = false);
 // decode_freq1 of an (uncompressed) order-1 table at [p, end) for 2^bits
 // slots: *used = its bytes.
 bool rans_parse_o1(const uint8_t *p, const uint8_t *end, int bits, std::vector<uint32_t> &F,
@@ -42,6 +43,17 @@ bool rans_dec_o0(const uint32_t *F, int bits, const uint8_t *in, size_t in_len, 
 // only in what a damaged stream decodes from a context without a row.
 bool rans_dec_o1(const uint32_t *F, const uint8_t *alpha, size_t rows, int bits, bool split_table,
                  const uint8_t *in, size_t in_len, uint8_t *out, size_t n);
+
+// One entropy stream (table, nx states, words; `len` bytes to the stream's
+// end) decoded as the reference decodes a stream that runs out of words: a
+// state below 2^15 stays as it is once fewer than two bytes are left
+// (RansDecRenormSafe), and the decode goes on.  The planner's slow path for a
+// chain the kernels report starved (status -1), and its check of a stream of
+// n = 0 symbols, whose table and states the reference still reads.  False
+// where the reference returns NULL: a short stream, a table it refuses, a
+// state below 2^15.  A context without a row decodes symbol 0 from a zeroed
+// row.  Reads stay inside [in, in + len), writes inside [out, out + n).
+bool rans_dec_ref(const uint8_t *in, uint32_t len, uint8_t *out, uint32_t n, bool o1, int nx);
 
 // A whole rans_compress_4x16 stream whose order byte has only the order-1
 // and NOSZ bits set (a compressed order-1 table is decoded here too);

@@ -215,6 +215,30 @@ struct UnRleItem {
 
 constexpr uint32_t RLE_CHUNK = 65536;
 
+// The expansion's run arithmetic.  A run length is whatever 32-bit value the
+// stream's varint holds, so every size (per literal, thread, chunk and item)
+// saturates at nout + 1, "does not fit", and never wraps; nout < 2^32 - 1.
+// unrle_span: the bytes a literal with run r stands for.  unrle_add: two
+// sizes, or an offset and a size.  unrle_fill: how many of a span's bytes at
+// offset o lie inside the output, the only trip count of the write loop.
+__host__ __device__ inline uint32_t unrle_span(uint32_t r, uint32_t nout) {
+    return r >= nout ? nout + 1 : r + 1;
+}
+__host__ __device__ inline uint32_t unrle_add(uint32_t a, uint32_t b, uint32_t nout) {
+    const uint64_t v = uint64_t(a) + b;
+    return v > nout ? nout + 1 : uint32_t(v);
+}
+__host__ __device__ inline uint32_t unrle_fill(uint32_t o, uint32_t span, uint32_t nout) {
+    if (o >= nout) return 0;
+    return span < nout - o ? span : nout - o;
+}
+// the big-endian varint in runs[s..e] (var_get_u32's arithmetic, varint.h:267)
+__host__ __device__ inline uint32_t unrle_varint(const uint8_t *runs, uint32_t s, uint32_t e) {
+    uint32_t v = 0;
+    for (uint32_t i = s; i <= e; i++) v = (v << 7) | (runs[i] & 0x7f);
+    return v;
+}
+
 hipError_t launch_rle_count(const RleItem *items, const uint32_t *chunk_item,
                             int nchunks, uint32_t *cstat, hipStream_t s);
 hipError_t launch_rle_emit(const RleItem *items, const uint32_t *chunk_item,

@@ -93,6 +93,7 @@ class Decompressor {
     bool parse_o0_table(DJ &j, const uint8_t *p, const uint8_t *end, uint32_t *used);
     bool parse_o1_table(DJ &j, const uint8_t *p, const uint8_t *end);
     void run_djs(const std::vector<int> &ids, bool may_host);
+    void starved(DJ &j);
 };
 
 int Decompressor::add_dj(const uint8_t *h, const uint8_t *d, uint32_t len, uint32_t n,
@@ -136,7 +137,7 @@ int Decompressor::add_dj(const uint8_t *h, const uint8_t *d, uint32_t len, uint3
 bool Decompressor::parse_o0_table(DJ &j, const uint8_t *p, const uint8_t *end,
                                   uint32_t *used) {
     j.bits = 12;
-    return host::rans_parse_o0(p, end, j.F, used);
+    return host::rans_parse_o0(p, end, j.F, used, j.nx == 32);
 }
 
 // decode_freq1 (rANS_static16_int.h:468-536).  Sets tab_len for the
@@ -260,8 +261,9 @@ int Decompressor::parse(const uint8_t *h, const uint8_t *d, uint32_t len, uint8_
     else L.d_ent = d_out;
     if (rest && !L.cat && L.ent_n)
         L.dj_main = add_dj(h + p, d + p, rest, L.ent_n, o1, x32 ? 32 : 4, L.d_ent);
-    else if (rest && !L.cat && !L.ent_n)
-        L.dj_main = -1;
+    else if (rest && !L.cat && !L.ent_n &&
+             !host::rans_dec_ref(h + p, rest, nullptr, 0, o1, x32 ? 32 : 4))
+        return id;        // no symbols, yet the reference reads the table and the states
     L.ok = true;
     nodes_[id] = std::move(L);
     return id;
@@ -330,6 +332,20 @@ std::atomic<uint64_t> g_dec_variant[DV_COUNT], g_dec_variant_hedged[DV_COUNT];
 inline int chain_kind(const DJ &j) { return j.o1 ? host::CK_RANS_O1 : host::CK_RANS_O0; }
 
 void Decompressor::run_djs(const std::vector<int> &ids, bool may_host) {
+    // A state word below 2^15 is refused before any symbol is decoded, as the
+    // reference does (rANS_static4x16pr.c:291-294, :650-653; the 32-state
+    // decoders alike).  The chains themselves would renormalise such a state
+    // and go on wherever the stream has words to spare.
+    for (int id : ids) {
+        DJ &j = djs_[id];
+        if (!j.ok || !j.n) continue;
+        if (j.len < j.tab_len + 4u * j.nx) { j.ok = false; continue; }
+        const uint8_t *s = j.h + j.tab_len;
+        for (int z = 0; z < j.nx && j.ok; z++, s += 4) {
+            const uint32_t x = s[0] | uint32_t(s[1]) << 8 | uint32_t(s[2]) << 16 | uint32_t(s[3]) << 24;
+            if (x < (1u << 15)) j.ok = false;
+        }
+    }
     // ---- the chains that decode on host cores (host::place by
     // host_decode_mode() among the 4-state chains).  They start now, into
     // pinned staging, and are joined after the launch below.
@@ -388,7 +404,7 @@ void Decompressor::run_djs(const std::vector<int> &ids, bool may_host) {
         for (HostChain &c : hc) {
             DJ &j = djs_[c.id];
             host_longest_ms_ = std::max(host_longest_ms_, c.ns * 1e-6);
-            if (!c.ok) { j.ok = false; continue; }
+            if (!c.ok) { starved(j); continue; }
             host::measured(chain_kind(j), false, j.n, c.ns);
             FQZ5_HIP(hipMemcpyAsync(j.d_out, c.buf, j.n, hipMemcpyHostToDevice, g_.stream));
         }
@@ -553,7 +569,21 @@ void Decompressor::run_djs(const std::vector<int> &ids, bool may_host) {
         if (prof_on()) prof_add(PK_RANS_DEC, ms, bytes);
     }
     for (size_t k = 0; k < used.size(); k++)
-        if (st[k]) djs_[used[k]].ok = false;
+        if (st[k]) starved(djs_[used[k]]);
+}
+
+// A chain that took more words than its stream has (the kernels' status -1,
+// the host decoders' false).  The reference does not refuse such a stream: a
+// state that finds no word left stays as it is and the decode goes on
+// (RansDecRenormSafe).  The kernels keep their one check at the end of the
+// chain; the stream is decoded again here, on the host, with the reference's
+// rule, and its bytes replace the chain's.
+void Decompressor::starved(DJ &j) {
+    std::vector<uint8_t> buf(size_t(j.n) + 1);
+    j.ok = host::rans_dec_ref(j.h, j.len, buf.data(), j.n, j.o1, j.nx);
+    if (!j.ok) return;
+    FQZ5_HIP(hipMemcpyAsync(j.d_out, buf.data(), j.n, hipMemcpyHostToDevice, g_.stream));
+    g_.sync();
 }
 
 void Decompressor::run(std::vector<DecompressReq> &reqs) {
@@ -614,7 +644,8 @@ void Decompressor::run(std::vector<DecompressReq> &reqs) {
     for (size_t i = 0; i < nodes_.size(); i++) {
         Node &N = nodes_[i];
         if (!N.stripe && N.ok && N.rle) {
-            if (!N.meta_len) { N.ok = false; continue; }
+            // (sizes saturate at osz + 1: kernels.h unrle_add)
+            if (!N.meta_len || N.osz == UINT32_MAX) { N.ok = false; continue; }
             rl.push_back(int(i));
         }
     }
@@ -696,19 +727,27 @@ void Decompressor::run(std::vector<DecompressReq> &reqs) {
             FQZ5_HIP(launch_unrle_expand(d_items, d_cil, nl, d_coff, d_cl, 0, g_.stream));
             g_.download(cl.data(), d_cl, nl);
             g_.sync();
+            bool failed = false;
             {
-                std::vector<uint64_t> acc(items.size(), 0);
+                // sizes saturate at nout + 1 (kernels.h unrle_add), a chunk's
+                // and an item's as a thread's did
+                std::vector<uint32_t> acc(items.size(), 0);
                 for (int c = 0; c < nl; c++) {
                     uint32_t w = ci_lit[2 * c];
-                    coff_lit[2 * c + 1] = uint32_t(acc[w]);
-                    acc[w] += cl[c];
+                    coff_lit[2 * c + 1] = acc[w];
+                    acc[w] = unrle_add(acc[w], cl[c], items[w].nout);
                 }
                 for (size_t k = 0; k < items.size(); k++) {
                     Node &N = nodes_[who[k]];
-                    N.unrle_len = uint32_t(acc[k]);
-                    if (acc[k] > N.osz) N.ok = false;     // rle.c:171 overflow
+                    N.unrle_len = acc[k];
+                    if (acc[k] > N.osz) {                 // rle.c:171 overflow
+                        N.ok = false;
+                        items[k].nlit = 0;                // nothing of it is written
+                        failed = true;
+                    }
                 }
             }
+            if (failed) d_items = g_.upload(items);
             FQZ5_HIP(launch_unrle_expand(d_items, d_cil, nl, g_.upload(coff_lit), d_cl, 1,
                                          g_.stream));
         }

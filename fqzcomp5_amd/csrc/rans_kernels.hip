@@ -462,16 +462,40 @@ __global__ __launch_bounds__(256) void k_unrle_vend(const UnRleItem *items,
         if (!(it.runs[i] & 0x80)) it.vend[k++] = i;
 }
 
+// Run length k: varint k spans (vend[k-1], vend[k]].  Bytes after the last
+// terminator are the varint the reference reads up to the end of the
+// meta-data (varint.h:291); past those every run is 0.
 static DEV uint32_t unrle_run(const UnRleItem &it, uint32_t k) {
-    // varint k spans (vend[k-1], vend[k]]
-    uint32_t s = k ? it.vend[k - 1] + 1 : 0, e = it.vend[k];
-    uint32_t v = 0;
-    for (uint32_t i = s; i <= e; i++) v = (v << 7) | (it.runs[i] & 0x7f);
-    return v;
+    if (k > it.nvarint) return 0;
+    const uint32_t s = k ? it.vend[k - 1] + 1 : 0;
+    if (k == it.nvarint) return s < it.nrun ? unrle_varint(it.runs, s, it.nrun - 1) : 0;
+    return unrle_varint(it.runs, s, it.vend[k]);
+}
+
+// Inclusive scan of sizes that saturate at nout + 1 (unrle_add); returns the
+// exclusive prefix.
+static DEV uint32_t block_excl_sat(uint32_t v, uint32_t nout, uint32_t *tmp, uint32_t *total) {
+    const int t = threadIdx.x;
+    tmp[t] = v;
+    __syncthreads();
+    uint32_t acc = v;
+    for (int o = 1; o < 256; o <<= 1) {
+        uint32_t w = (t >= o) ? tmp[t - o] : 0;
+        __syncthreads();
+        acc = unrle_add(acc, w, nout);
+        tmp[t] = acc;
+        __syncthreads();
+    }
+    if (total) *total = tmp[255];
+    const uint32_t ex = t ? tmp[t - 1] : 0;
+    __syncthreads();
+    return ex;
 }
 
 // what 0: per chunk output length; what 1: write.  coff: {rle-literal
-// offset, output offset} per chunk.
+// offset, output offset} per chunk.  Every size and offset saturates at
+// nout + 1 (kernels.h unrle_*), so the host's "larger than nout" test sees
+// every overflow and the write loop runs at most nout - o times.
 __global__ __launch_bounds__(256) void k_unrle_expand(const UnRleItem *items,
                                                       const uint32_t *chunk_item,
                                                       const uint32_t *coff,
@@ -491,11 +515,11 @@ __global__ __launch_bounds__(256) void k_unrle_expand(const UnRleItem *items,
     uint32_t olen = 0, k0 = k;
     for (uint32_t i = a; i < b; i++) {
         uint32_t r = 0;
-        if (saved[it.lits[i]]) { r = k < it.nvarint ? unrle_run(it, k) : 0; k++; }
-        olen += r + 1;
+        if (saved[it.lits[i]]) r = unrle_run(it, k++);
+        olen = unrle_add(olen, unrle_span(r, it.nout), it.nout);
     }
     uint32_t tot;
-    uint32_t o = block_excl_sum(olen, tmp, &tot) + coff[2 * c + 1];
+    uint32_t o = unrle_add(block_excl_sat(olen, it.nout, tmp, &tot), coff[2 * c + 1], it.nout);
     if (what == 0) {
         if (threadIdx.x == 0) cstat[c] = tot;
         return;
@@ -504,10 +528,10 @@ __global__ __launch_bounds__(256) void k_unrle_expand(const UnRleItem *items,
     for (uint32_t i = a; i < b; i++) {
         uint32_t r = 0;
         uint8_t ch = it.lits[i];
-        if (saved[ch]) { r = k < it.nvarint ? unrle_run(it, k) : 0; k++; }
-        for (uint32_t j = 0; j <= r; j++)
-            if (o + j < it.nout) it.out[o + j] = ch;
-        o += r + 1;
+        if (saved[ch]) r = unrle_run(it, k++);
+        const uint32_t span = unrle_span(r, it.nout), fill = unrle_fill(o, span, it.nout);
+        for (uint32_t j = 0; j < fill; j++) it.out[o + j] = ch;
+        o = unrle_add(o, span, it.nout);
     }
 }
 

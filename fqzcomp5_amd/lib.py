@@ -207,6 +207,19 @@ def fqz_div_selftest() -> int:
     return int(so.fqz5_fqz_div_selftest())
 
 
+def unrle_selftest(runs: bytes, nlit: int, nout: int, o: int = 0):
+    """The RLE expansion's run arithmetic on the host (fqz5_unrle_selftest):
+    (end offset saturated at nout + 1, write-loop trips, longest fill)."""
+    so = load()
+    so.fqz5_unrle_selftest.restype = C.c_int
+    so.fqz5_unrle_selftest.argtypes = [C.c_char_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint,
+                                       C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 3)()
+    if so.fqz5_unrle_selftest(bytes(runs), len(runs), nlit, nout, o, out):
+        raise NativeError("fqz5_unrle_selftest: a fill passes nout")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
 def device_ok() -> bool:
     return bool(load().fqz5_device_ok())
 

@@ -441,6 +441,15 @@ int fqz5_seq_decode_many(int n, const unsigned char *const *in, const unsigned i
  * Returns the number of mismatches (0), or -1 on a device error. */
 long fqz5_fqz_div_selftest(void);
 
+/* Host check of the RLE expansion's run arithmetic (no device): one thread's
+ * walk over nlit RLE-symbol literals from output offset o, whose runs are
+ * the varints of runs[0..nrun), into an output of nout bytes.  out3: the end
+ * offset, saturated at nout + 1 (larger than nout: the stream is refused),
+ * the trips of the write loop, the longest single fill.  Returns 0, or -1
+ * if a fill would pass nout. */
+int fqz5_unrle_selftest(const unsigned char *runs, unsigned nrun, unsigned nlit, unsigned nout,
+                        unsigned o, uint64_t *out3);
+
 #ifdef __cplusplus
 }
 #endif

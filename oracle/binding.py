@@ -128,6 +128,21 @@ class _Codec:
         p = self._ru(bytes(comp), len(comp), C.byref(n))
         return self._take(p, n.value)
 
+    def rans_uncompress_to(self, comp: bytes, cap: int):
+        """rans_uncompress_to_4x16 into a caller buffer of `cap` bytes (the
+        size itself for a NOSZ stream); None where it returns NULL."""
+        f = getattr(self, "_rut", None)
+        if f is None:
+            f = getattr(self.lib, self._prefix + "rans_uncompress_to_4x16")
+            f.restype = C.c_void_p
+            f.argtypes = [C.c_char_p, C.c_uint, C.c_void_p, C.POINTER(C.c_uint)]
+            self._rut = f
+        inb = C.create_string_buffer(bytes(comp), max(len(comp), 1))
+        buf = C.create_string_buffer(max(cap, 1))
+        n = C.c_uint(cap)
+        p = f(inb, len(comp), buf, C.byref(n))
+        return None if not p else buf.raw[:n.value]
+
     def tok3_encode(self, names: bytes, level: int, use_arith: int = 0):
         """tok3_encode_names (tokenise_name3.c:1451) on a private copy of
         `names`: (stream, last_start), or None where it returns NULL."""

@@ -334,11 +334,17 @@ static int enc_o0(const uint8_t *in, uint32_t n, uint8_t *out,
 /* O0 decode table: slot -> (sym, freq, slot-start) */
 typedef struct { uint8_t sym[4096]; uint16_t f[256], b[256]; } o0tab_t;
 
-static int build_o0tab(const uint32_t *F, int bits, o0tab_t *t) {
+/* skip: a symbol whose frequency does not fit the slots left is passed over,
+ * as the 32-state order-0 decoder does (rans_F_to_s3, rANS_static16_int.h:540);
+ * the 4-state decoders refuse the table (rANS_static4x16pr.c:273, :621). */
+static int build_o0tab(const uint32_t *F, int bits, o0tab_t *t, int skip) {
     uint32_t x = 0;
     for (int j = 0; j < 256; j++) {
         if (!F[j]) continue;
-        if (F[j] > (1u << bits) - x) return -1;
+        if (F[j] > (1u << bits) - x) {
+            if (skip) continue;
+            return -1;
+        }
         t->f[j] = (uint16_t)F[j];
         t->b[j] = (uint16_t)x;
         memset(&t->sym[x], j, F[j]);
@@ -377,7 +383,7 @@ static int dec_o0(const uint8_t *in, uint32_t in_size, uint8_t *out,
     if (!hs) return -1;
     normalise_freq_shift(F, tot, 4096);
     o0tab_t *t = malloc(sizeof(*t));
-    if (!t || build_o0tab(F, 12, t)) { free(t); return -1; }
+    if (!t || build_o0tab(F, 12, t, NX == 32)) { free(t); return -1; }
     rbuf_t r = { in + hs, in + in_size };
     uint32_t R[32];
     if (read_states(R, NX, &r)) { free(t); return -1; }
@@ -539,6 +545,9 @@ static int dec_o1(const uint8_t *in, uint32_t in_size, uint8_t *out,
     const uint8_t *cp = in, *end = in + in_size, *tab_end = NULL;
     uint8_t *ubuf = NULL;
     int shift = *cp >> 4;
+    /* the tables hold 2^12 slots a row.  (The reference takes any shift and
+     * lays a row of 2^13 and more slots over the rows behind it.) */
+    if (shift > 12) return -1;
     const uint8_t *hend = end;
     if (*cp++ & 1) {
         uint32_t u, c;
@@ -554,6 +563,10 @@ static int dec_o1(const uint8_t *in, uint32_t in_size, uint8_t *out,
     uint32_t A[256] = {0};
     int k = decode_alphabet(cp, hend, A);
     if (!k) { free(ubuf); return -1; }
+    /* every state starts in context 0.  Without a row for it the reference
+     * decodes from whatever an earlier call left in its thread-local tables,
+     * an outcome that is no function of the stream: refused here. */
+    if (!A[0]) { free(ubuf); return -1; }
     cp += k;
     o0tab_t *tab = calloc(256, sizeof(o0tab_t));
     if (!tab) { free(ubuf); return -1; }
@@ -565,7 +578,7 @@ static int dec_o1(const uint8_t *in, uint32_t in_size, uint8_t *out,
         cp += k;
         if (!T) continue;
         normalise_freq_shift(F, T, 1u << shift);
-        if (build_o0tab(F, shift, &tab[i])) { free(ubuf); free(tab); return -1; }
+        if (build_o0tab(F, shift, &tab[i], 0)) { free(ubuf); free(tab); return -1; }
     }
     if (tab_end) cp = tab_end;
     free(ubuf);
