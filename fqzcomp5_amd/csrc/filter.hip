@@ -4,16 +4,16 @@
 // and complexity (the rule: include/fqz5_fastq.h).
 //
 // Two kernels per block:
-//   k_filter_sums  streams the bases and the qualities over the tiles of
-//                  stats_tile.hpp (stats.hip's machinery, without its
+//   k_filter_sums  streams the bases and the qualities with the tile walk of
+//                  record_tile.hpp (the one k_stats_tiles runs, without its
 //                  histograms) and leaves five sums per record: n, gc and
 //                  diff from the bases, qsum and lowq from the qualities.  A
-//                  lane walks the records across its 16-byte chunk and adds a
-//                  record's partial sums once: to the tile's LDS cells of
-//                  that record (flushed to the record's global cells once per
-//                  tile), or, past ST_KCAP records of one tile, straight to
-//                  the global cells.  diff at position p needs byte p + 1: it
-//                  is the next byte of the chunk, or for the chunk's last
+//                  record's partial sums of one chunk are added once: to the
+//                  tile's LDS cells of that record (flushed to the record's
+//                  global cells once per tile), or, past ST_KCAP records of
+//                  one tile, straight to the global cells.  diff at position
+//                  p needs byte p + 1: it is the next byte of the chunk, or
+//                  for the chunk's last
 //                  position one byte read on its own (the next chunk's first,
 //                  which may be the next tile's first); it counts only when
 //                  p + 1 lies before the end of p's record, which at a tile's
@@ -37,8 +37,7 @@
 
 #include "../../include/fqz5_fastq.h"
 #include "gpu_ctx.hpp"
-#include "name_match.hpp"
-#include "stats_tile.hpp"
+#include "record_tile.hpp"
 
 namespace fqz5 {
 GpuCtx &gpu();
@@ -98,23 +97,29 @@ __global__ __launch_bounds__(ST_THREADS) void k_filter_sums(
         __syncthreads();                        // (the last tile's flush has read lsum)
         T.stage(lend);
         __syncthreads();
-        const int64_t t0 = int64_t(T.t0), tend = t0 + T.n;
+        const int64_t tend = int64_t(T.t0) + T.n;
         for (uint32_t s = 0; s < 2; s++) {
             const uint8_t *src = s ? qual : seq;
             if (!src) continue;
-            const int64_t w0 = t0 - int64_t((reinterpret_cast<uintptr_t>(src) + T.t0) & 15u);
-            for (uint32_t i = threadIdx.x;; i += ST_THREADS) {
-                const int64_t a = w0 + 16 * int64_t(i);
-                if (a >= tend) break;
+            tile_chunks(T, src, [&](int64_t a) {
                 const uint4 v = load16(src, seq_len, a);
                 // the byte after the chunk, for diff at the chunk's last position
                 // when that is one of the tile's (a + 15 >= t0 always)
                 uint32_t after = 0;
                 if (!s && a + 15 < tend && uint64_t(a + 16) < seq_len) after = src[a + 16];
                 const uint32_t w[5] = {v.x, v.y, v.z, v.w, after};
-                uint32_t k = T.owner(uint32_t((a > t0 ? a : t0) - t0));
-                uint32_t ek = T.relend(k), acc0 = 0, acc1 = 0, acc2 = 0;
-                const auto put = [&](uint32_t rec) {
+                ChunkWalk W(T, a);
+                uint32_t acc0 = 0, acc1 = 0, acc2 = 0;
+                W.bytes(T, a, v, [&](uint32_t q, uint32_t k, uint32_t c, int b) {
+                    acc0 += s ? c : is_n(c);
+                    acc1 += s ? c < low_q : is_gc(c);
+                    if (s) return;
+                    const uint32_t nx = (w[(b + 1) >> 2] >> (8 * ((b + 1) & 3))) & 0xFFu;
+                    if (c == nx) return;
+                    // is p + 1 still in p's record?  ek is clipped to the tile:
+                    // at the tile's last position the record's own end decides
+                    if (q + 1 < W.ek || (q + 1 == ST_TILE && T.end[T.r0 + k] > T.t0 + ST_TILE)) acc2++;
+                }, [&](uint32_t rec) {
                     if (rec < ST_KCAP) {
                         uint32_t *cell = lsum + (s ? 3 : 0) * ST_KCAP + rec;
                         if (acc0) atomicAdd(cell, acc0);
@@ -129,44 +134,14 @@ __global__ __launch_bounds__(ST_THREADS) void k_filter_sums(
                         if (acc2) atomicAdd(out.diff + T.r0 + rec, acc2);
                     }
                     acc0 = acc1 = acc2 = 0;
-                };
-#pragma unroll
-                for (int b = 0; b < 16; b++) {
-                    const int64_t p = a + b;
-                    if (p < t0 || p >= tend) continue;
-                    const uint32_t q = uint32_t(p - t0);
-                    if (q >= ek) {
-                        put(k);
-                        do ek = T.relend(++k); while (q >= ek);
-                    }
-                    const uint32_t c = (w[b >> 2] >> (8 * (b & 3))) & 0xFFu;
-                    if (s) {
-                        acc0 += c;
-                        acc1 += c < low_q;
-                        continue;
-                    }
-                    acc0 += is_n(c);
-                    acc1 += is_gc(c);
-                    const uint32_t nx = (w[(b + 1) >> 2] >> (8 * ((b + 1) & 3))) & 0xFFu;
-                    if (c == nx) continue;
-                    // is p + 1 still in p's record?  ek is clipped to the tile:
-                    // at the tile's last position the record's own end decides
-                    if (q + 1 < ek || (q + 1 == ST_TILE && T.end[T.r0 + k] > T.t0 + ST_TILE)) acc2++;
-                }
-                put(k);
-            }
+                });
+            });
         }
         __syncthreads();
-        const uint32_t k1 = T.nrt < ST_KCAP ? T.nrt : ST_KCAP;
-        for (uint32_t k = threadIdx.x; k < k1; k += ST_THREADS) {
-            const uint32_t r = T.r0 + k;
-            uint32_t x;
-            if ((x = lsum[k])) { atomicAdd(out.n + r, x); lsum[k] = 0; }
-            if ((x = lsum[ST_KCAP + k])) { atomicAdd(out.gc + r, x); lsum[ST_KCAP + k] = 0; }
-            if ((x = lsum[2 * ST_KCAP + k])) { atomicAdd(out.diff + r, x); lsum[2 * ST_KCAP + k] = 0; }
-            if ((x = lsum[3 * ST_KCAP + k])) { flush_cell(out.qsum + r, x); lsum[3 * ST_KCAP + k] = 0; }
-            if ((x = lsum[4 * ST_KCAP + k])) { atomicAdd(out.lowq + r, x); lsum[4 * ST_KCAP + k] = 0; }
-        }
+        flush_records<FT_SUMS>(T, lsum, [&](uint32_t j, uint32_t r, uint32_t x) {
+            if (j == 3) flush_cell(out.qsum + r, x);
+            else atomicAdd((j == 0 ? out.n : j == 1 ? out.gc : j == 2 ? out.diff : out.lowq) + r, x);
+        });
     }
 }
 
@@ -210,9 +185,7 @@ std::vector<uint64_t> check_call(const fqz5_filter_spec *f, bool has_seq, bool h
         throw GpuError(std::string(who) + ": a base criterion without the bases");
     if (qual_criterion(*f) && !has_qual)
         throw GpuError(std::string(who) + ": a quality criterion without the qualities");
-    if (nrec >= (1ull << 31)) throw GpuError(std::string(who) + ": block too large");
-    if (pairs && (nrec & 1))
-        throw GpuError(std::string(who) + ": an odd record count in a block of pairs");
+    check_records(nrec, pairs, who);
     return record_ends(lens, nrec, seq_len, who);
 }
 

@@ -14,16 +14,10 @@
 //                   grid-strides over the tiles, skipping those in which no
 //                   record can have a position inside its window.
 //   k_stats_bin     read_qual and read_gc from the per-read sums.
-// (The tiles, the record ends in LDS and the loads are stats_tile.hpp's,
-// shared with filter.hip.)
-// The record that owns a base comes from the records' ends: the host gives
-// each tile its first record (a merge of the ends with the tile grid), the
-// workgroup stages the tile's ends into LDS, a lane searches them once for
-// the first byte of its 16-byte chunk and walks from there; equal ends (empty
-// records) are stepped over and never own a base.
-// Both arrays are streamed with 16-byte loads at 16-byte addresses, each by
-// its own alignment (k_seq_match's staging rule: a chunk that is not wholly
-// inside [0, seq_len) is read byte by byte, never outside).  No table is
+// The tiles, the walk that gives every base its record, the loads and the
+// flush of the per-read sums are record_tile.hpp's, shared with filter.hip:
+// both arrays are streamed in 16-byte chunks at 16-byte addresses, each by
+// its own alignment, and never read outside [0, seq_len).  No table is
 // touched by a global atomic per base: LDS cells are u32, bounded by the bases
 // of one launch (at most 2^31, launches are split), and flushed once per
 // workgroup, non-zero cells only.
@@ -35,8 +29,7 @@
 
 #include "../../include/fqz5_fastq.h"
 #include "gpu_ctx.hpp"
-#include "name_match.hpp"
-#include "stats_tile.hpp"
+#include "record_tile.hpp"
 
 namespace fqz5 {
 GpuCtx &gpu();
@@ -95,54 +88,31 @@ __global__ __launch_bounds__(ST_THREADS) void k_stats_tiles(
         __syncthreads();                        // (the last tile's flush has read lsum)
         T.stage(lend);
         __syncthreads();
-        const int64_t t0 = int64_t(T.t0), tend = t0 + T.n;
         for (uint32_t s = 0; s < 2; s++) {
             const uint8_t *src = s ? qual : seq;
             if (!src) continue;
-            const int64_t w0 = t0 - int64_t((reinterpret_cast<uintptr_t>(src) + T.t0) & 15u);
-            for (uint32_t i = threadIdx.x;; i += ST_THREADS) {
-                const int64_t a = w0 + 16 * int64_t(i);
-                if (a >= tend) break;
+            tile_chunks(T, src, [&](int64_t a) {
                 const uint4 v = load16(src, seq_len, a);
-                uint32_t k = T.owner(uint32_t((a > t0 ? a : t0) - t0));
-                uint32_t ek = T.relend(k), acc = 0;
-                const auto put = [&](uint32_t rec, uint32_t sum) {
+                ChunkWalk W(T, a);
+                uint32_t acc = 0;
+                W.bytes(T, a, v, [&](uint32_t, uint32_t k, uint32_t c, int) {
+                    atomicAdd(&hist[(s * 2 + ((T.r0 + k) & pair)) * 256 + c], 1u);
+                    acc += s ? c : is_gc(c);
+                }, [&](uint32_t rec) {
+                    const uint32_t sum = acc;
+                    acc = 0;
                     if (!sum) return;
                     if (rec < ST_KCAP) atomicAdd(&lsum[s * ST_KCAP + rec], sum);
-                    else if (s) atomicAdd(reinterpret_cast<unsigned long long *>(rec_qsum + T.r0 + rec),
-                                          static_cast<unsigned long long>(sum));
+                    else if (s) flush_cell(rec_qsum + T.r0 + rec, sum);
                     else atomicAdd(rec_gc + T.r0 + rec, sum);
-                };
-                const auto word = [&](uint32_t w, int at) {
-#pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        const int64_t p = a + at + j;
-                        if (p < t0 || p >= tend) continue;
-                        const uint32_t q = uint32_t(p - t0);
-                        if (q >= ek) {
-                            put(k, acc);
-                            acc = 0;
-                            do ek = T.relend(++k); while (q >= ek);
-                        }
-                        const uint32_t c = (w >> (8 * j)) & 0xFFu;
-                        atomicAdd(&hist[(s * 2 + ((T.r0 + k) & pair)) * 256 + c], 1u);
-                        acc += s ? c : is_gc(c);
-                    }
-                };
-                word(v.x, 0);
-                word(v.y, 4);
-                word(v.z, 8);
-                word(v.w, 12);
-                put(k, acc);
-            }
+                });
+            });
         }
         __syncthreads();
-        const uint32_t k1 = T.nrt < ST_KCAP ? T.nrt : ST_KCAP;
-        for (uint32_t k = threadIdx.x; k < k1; k += ST_THREADS) {
-            const uint32_t g = lsum[k], q = lsum[ST_KCAP + k];
-            if (g) { atomicAdd(rec_gc + T.r0 + k, g); lsum[k] = 0; }
-            if (q) { flush_cell(rec_qsum + T.r0 + k, q); lsum[ST_KCAP + k] = 0; }
-        }
+        flush_records<2>(T, lsum, [&](uint32_t j, uint32_t r, uint32_t x) {
+            if (j) flush_cell(rec_qsum + r, x);
+            else atomicAdd(rec_gc + r, x);
+        });
     }
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < 2 * 2 * 256; i += ST_THREADS) {
@@ -185,42 +155,21 @@ __global__ __launch_bounds__(ST_THREADS) void k_stats_cycles(
         for (uint32_t s = 0; s < 2; s++) {
             const uint8_t *src = s ? qual : seq;
             if (!src) continue;
-            const int64_t w0 = t0 - int64_t((reinterpret_cast<uintptr_t>(src) + T.t0) & 15u);
-            for (uint32_t i = threadIdx.x;; i += ST_THREADS) {
-                const int64_t a = w0 + 16 * int64_t(i);
-                if (a >= tend) break;
-                const uint32_t q0 = uint32_t((a > t0 ? a : t0) - t0);
-                uint32_t k = T.owner(q0);
-                uint32_t ek = T.relend(k);
-                int64_t st = T.start(k);
+            tile_chunks(T, src, [&](int64_t a) {
+                ChunkWalk W(T, a);
                 // the whole chunk inside one record and outside the window: no load
-                if (ek >= q0 + 16 && (uint64_t(int64_t(q0) - st) >= hi ||
-                                      uint64_t(int64_t(q0) + 15 - st) < lo))
-                    continue;
+                if (W.ek >= W.q0 + 16 && (uint64_t(int64_t(W.q0) - W.st) >= hi ||
+                                          uint64_t(int64_t(W.q0) + 15 - W.st) < lo))
+                    return;
                 const uint4 v = load16(src, seq_len, a);
-                const auto word = [&](uint32_t w, int at) {
-#pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        const int64_t p = a + at + j;
-                        if (p < t0 || p >= tend) continue;
-                        const uint32_t q = uint32_t(p - t0);
-                        while (q >= ek) {
-                            st = int64_t(ek);
-                            ek = T.relend(++k);
-                        }
-                        const uint64_t cyc = uint64_t(int64_t(q) - st);
-                        if (cyc < lo || cyc >= hi) continue;
-                        const uint32_t c = (w >> (8 * j)) & 0xFFu;
-                        const uint32_t cell = ((T.r0 + k) & pair) * win + uint32_t(cyc - lo);
-                        if (s) atomicAdd(&cq[cell * 256 + c], 1u);
-                        else atomicAdd(&cb[cell * 6 + base_class(c)], 1u);
-                    }
-                };
-                word(v.x, 0);
-                word(v.y, 4);
-                word(v.z, 8);
-                word(v.w, 12);
-            }
+                W.bytes(T, a, v, [&](uint32_t q, uint32_t k, uint32_t c, int) {
+                    const uint64_t cyc = uint64_t(int64_t(q) - W.st);
+                    if (cyc < lo || cyc >= hi) return;
+                    const uint32_t cell = ((T.r0 + k) & pair) * win + uint32_t(cyc - lo);
+                    if (s) atomicAdd(&cq[cell * 256 + c], 1u);
+                    else atomicAdd(&cb[cell * 6 + base_class(c)], 1u);
+                }, [](uint32_t) {});
+            });
         }
     }
     __syncthreads();
@@ -275,9 +224,7 @@ void check_shape(uint32_t cycles, int mates, uint64_t nrec, const char *who) {
     if (mates != 1 && mates != 2) throw GpuError(std::string(who) + ": mates is not 1 or 2");
     if (cycles < 1 || cycles > ST_CYCLES_MAX)
         throw GpuError(std::string(who) + ": cycles not in 1..65536");
-    if (nrec >= (1ull << 31)) throw GpuError(std::string(who) + ": block too large");
-    if (mates == 2 && (nrec & 1))
-        throw GpuError(std::string(who) + ": an odd record count in a block of pairs");
+    check_records(nrec, mates == 2, who);
 }
 
 }  // namespace

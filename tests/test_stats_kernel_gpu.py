@@ -117,6 +117,19 @@ def test_total_sizes(T, pads):
         _both(records, 100, mates=2, pads=pads, what=total)
 
 
+@pytest.mark.parametrize("mis_seq", range(16))
+def test_misaligned_views(T, mis_seq):
+    """The bases at every misalignment, the qualities at another: T + 5 bases
+    cut into records at T - 1, T and T + 1, cycles 64, so the long record's
+    chunks past the cycle window are skipped without a load at every
+    alignment of the chunk grid.  Against fqz5_stats_host."""
+    rng = random.Random(60 + mis_seq)
+    records = _records(rng, _cut(T + 5, [T - 1, T, T + 1]), alphabet=b"ACGTNacgt", quals=range(256))
+    got = _both(records, 64, pads=(mis_seq, (5 * mis_seq + 3) % 16), what=mis_seq)
+    R.same(got, _host(records, 64, 1), mis_seq)
+    assert int(got["cycle_base"].sum()) == 64 + 1 + 1 + 4
+
+
 @pytest.mark.parametrize("cycles", ["1", "64", "65", "2T"])
 def test_one_record_across_tiles(T, cycles):
     """One record of 3T + 5 bases: its sums cross three tile edges."""
