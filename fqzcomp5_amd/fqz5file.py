@@ -182,6 +182,17 @@ def _load():
         so.fqz5_filter_host.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_void_p,
                                         C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_void_p]
+        so.fqz5_trim_cuts.restype = C.c_int
+        so.fqz5_trim_cuts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                      C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]
+        so.fqz5_trim_gather.restype = C.c_int
+        so.fqz5_trim_gather.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        so.fqz5_trim_host.restype = C.c_int
+        so.fqz5_trim_host.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint64,
+                                      C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]
         _bound = True
     return so
 
@@ -199,7 +210,9 @@ def _load():
 # filter_records / filter_file: index, read, upload, keys (the blocks parsed
 # and CRC-checked, their key sections decoded; parse where the criteria need no
 # section), filter (the sums and pick kernels), decode, format, download,
-# write);
+# write; trim_records / trim_file: the same with trim, the cuts, the key
+# streams' compaction and the filter's kernels, in place of filter, and the
+# remaining streams' compaction inside format);
 # the stages end with what the library synchronises
 _TRACE = {}
 
@@ -2214,7 +2227,8 @@ class _NameTable(_Native):
 
 
 def _key_windows(rd, keys: tuple, stages: tuple, match, pairs: bool, extract: bool,
-                 plus_name: bool, with_qual: bool, device: str, window_bytes: int | None):
+                 plus_name: bool, with_qual: bool, device: str, window_bytes: int | None,
+                 block_hook=None):
     """One pass over the container behind `rd` (see above), window by window,
     for a lookup whose keys are the sections `keys` ((SEC_NAME,): by read
     name, (SEC_SEQ,): by sequence content, the filter by read metrics: none,
@@ -2228,7 +2242,11 @@ def _key_windows(rd, keys: tuple, stages: tuple, match, pairs: bool, extract: bo
     qualities under a SEC_QUAL key is an error that names it.  stages: the
     trace's names of the key stage and the match stage.  Yields (file record
     numbers of the window's hits, their query indices, the hits' text as
-    device tensors or None without `extract`; pairs: R1 and R2 text)."""
+    device tensors or None without `extract`; pairs: R1 and R2 text).
+    block_hook (the trimmer's): called before the format for every block with
+    hits, once all its sections are decoded, as block_hook(the block's device
+    addresses by section, which it may replace, its BlockView, its record
+    lengths); it returns the record lengths the text is laid out with."""
     import functools
     import torch
     so = _load()
@@ -2289,11 +2307,15 @@ def _key_windows(rd, keys: tuple, stages: tuple, match, pairs: bool, extract: bo
             if rest:
                 win.decode([section(j, sec) for j, sec, _ in rest])
         with _stage("format"):
+            flens = lens
+            if block_hook is not None:
+                flens = {j: block_hook(ptr[j], views[j], lens[j]) for j in sels}
+
             def fmt(j, out, cap):
                 size, s1 = C.c_uint64(0), C.c_uint64(0)
                 _check(so.fqz5_fastq_format_list(
                     ptr[j][S.SEC_NAME], views[j].name_ulen, ptr[j][S.SEC_SEQ],
-                    ptr[j].get(S.SEC_QUAL) if with_qual else None, lens[j].ctypes.data,
+                    ptr[j].get(S.SEC_QUAL) if with_qual else None, flens[j].ctypes.data,
                     len(lens[j]), sels[j].data_ptr(), int(sels[j].numel()), int(plus_name),
                     int(pairs), out, cap, C.byref(size), C.byref(s1)), "fqz5_fastq_format_list")
                 return int(size.value), int(s1.value)
@@ -2304,14 +2326,14 @@ def _key_windows(rd, keys: tuple, stages: tuple, match, pairs: bool, extract: bo
 
 
 def _lookup(rd, keys: tuple, stages: tuple, match, pairs, extract, plus_name, with_qual, device,
-            window_bytes, sink):
+            window_bytes, sink, block_hook=None):
     """_key_windows run to its end: (the hits' file record numbers, their
     query indices, the bytes sink(windows of texts) wrote with `extract`)."""
     recs, qidx = [], []
 
     def windows():
         for r, q, texts in _key_windows(rd, keys, stages, match, pairs, extract, plus_name,
-                                        with_qual, device, window_bytes):
+                                        with_qual, device, window_bytes, block_hook):
             recs.append(r)
             qidx.append(q)
             yield texts
@@ -2814,8 +2836,8 @@ def stats(src, cycles: int = 1024, pairs: bool = False, per_record: bool = False
 # each block's records and picks on the device, and the remaining sections are
 # decoded in one further call for the blocks with hits alone.  The rule is
 # exact integer arithmetic (include/fqz5_fastq.h); a pair is kept only when
-# both mates pass.  One process.  Not built: trimming or clipping of records,
-# expected-error (maxee) filters, adapter-aware filters, several ranks.
+# both mates pass.  One process.  Not built: expected-error (maxee) filters,
+# several ranks (trimming, clipping and the adapter cut: "Trim and clip" below).
 # ---------------------------------------------------------------------------
 class _FilterSpec(C.Structure):
     """fqz5_filter_spec (include/fqz5_fastq.h)"""
@@ -3002,3 +3024,308 @@ def filter_file(src: str, dst: str, flt: Filter, plus_name: bool = False, device
     return _run((_PosFile(src), True), "filter", lambda rd: _filter(
         rd, flt, dst2 is not None, invert, True, plus_name, with_qual, device, window_bytes,
         lambda w: sum(_write_texts(outs, w))))
+
+
+# ---------------------------------------------------------------------------
+# Trim and clip
+#
+# "Clip fixed bases, trim low-quality ends, cut the 3' adapter, strip N ends,
+# crop, then filter what is left" (fastp, cutadapt): the pass of the filter,
+# with the records changed before they are judged and written.  The keys are
+# the sections the cut points are judged on (none for clip and crop alone,
+# SEC_SEQ for adapters or trim_n, SEC_SEQ and SEC_QUAL for a quality cutoff)
+# together with the filter's.  Per block fqz5_trim_cuts (trim.hip) finds every
+# record's kept interval on the device, fqz5_trim_gather compacts the key
+# streams to those intervals into buffers of their own, and from there they are
+# ordinary streams with new lengths: fqz5_filter_match judges them (an empty
+# Filter selects every record) and fqz5_fastq_format_list lays out their text,
+# both unchanged.  Sections that were no key are decoded for the blocks with
+# selected records as in every lookup and compacted before the format
+# (_key_windows' block_hook).  Names are never trimmed, and a record trimmed to
+# nothing is still a record; only the Filter drops records (its min_len is the
+# "too short after trimming" rule).  The rule is exact integer arithmetic
+# (include/fqz5_fastq.h).  One process.  Not built: poly-G / poly-X tails, 5'
+# and linked adapters, indels in the adapter match, wildcards and case folding,
+# paired-overlap adapter detection, several ranks, writing .fqz5 directly.
+# ---------------------------------------------------------------------------
+TRIM_ADAPTERS, TRIM_ADAPTER_MAX = 16, 128
+
+
+class _TrimSpec(C.Structure):
+    """fqz5_trim_spec (include/fqz5_fastq.h)"""
+    _fields_ = [("set", C.c_uint32), ("q5", C.c_uint32), ("q3", C.c_uint32),
+                ("min_overlap", C.c_uint32), ("max_err_pct", C.c_uint32),
+                ("n_adapters", C.c_uint32 * 2), ("head", C.c_uint64), ("tail", C.c_uint64),
+                ("max_len", C.c_uint64)]
+
+
+class _TrimAdapters(C.Structure):
+    """fqz5_trim_adapters"""
+    _fields_ = [("len", C.c_uint32 * (2 * TRIM_ADAPTERS)),
+                ("bytes", (C.c_uint8 * TRIM_ADAPTER_MAX) * (2 * TRIM_ADAPTERS))]
+
+
+class Trim:
+    """The steps of trim_records / trim_file, applied to every record in this
+    order; one left None (False, no adapters) is off.  Integers throughout,
+    the rule exact (include/fqz5_fastq.h); a quality is the quality line's
+    byte - 33:
+      head, tail     fixed bases off the 5' and the 3' end
+      q5, q3         the low-quality 5' / 3' end by the running-sum rule of BWA
+                     and cutadapt, each judged on what the clip left
+      adapters       3' adapters (bytes or str): the record is cut at the first
+                     position where one matches over min(its length, what is
+                     left of the read) >= min_overlap bases with at most
+                     max_err_pct percent of them mismatches (no indels, bytes
+                     compared as they are); adapters2: those of the odd
+                     records of interleaved pairs
+      trim_n         N and n off both ends
+      max_len        at most that many bases from the 5' end of what is left
+    ValueError: a negative value, a cutoff over 93, max_err_pct over 100,
+    min_overlap below 1, an empty adapter or one longer than 128 bytes, more
+    than 16 adapters per mate, adapters2 without adapters, min_overlap or
+    max_err_pct given without adapters."""
+
+    def __init__(self, head=None, tail=None, q5=None, q3=None, adapters=None, adapters2=None,
+                 min_overlap=3, max_err_pct=10, trim_n=False, max_len=None):
+        import operator
+        vals = {"head": head, "tail": tail, "q5": q5, "q3": q3, "min_overlap": min_overlap,
+                "max_err_pct": max_err_pct, "max_len": max_len}
+        for k, v in vals.items():
+            if v is None:
+                continue
+            vals[k] = v = operator.index(v)
+            if v < 0:
+                raise ValueError(f"Trim: {k} is negative")
+            if k in ("q5", "q3") and v > 93:
+                raise ValueError(f"Trim: {k} is a cutoff over 93")
+        if vals["max_err_pct"] is None or vals["max_err_pct"] > 100:
+            raise ValueError("Trim: max_err_pct is a percentage up to 100")
+        if vals["min_overlap"] is None or vals["min_overlap"] < 1:
+            raise ValueError("Trim: min_overlap is at least 1")
+        mates = []
+        for what, given in (("adapters", adapters), ("adapters2", adapters2)):
+            if isinstance(given, (bytes, bytearray, str)):
+                given = [given]
+            got = list(_as_bytes(given or (), "adapter"))
+            if given is not None and not got:
+                raise ValueError(f"Trim: {what} is empty")
+            if len(got) > TRIM_ADAPTERS:
+                raise ValueError(f"Trim: more than {TRIM_ADAPTERS} {what}")
+            for a in got:
+                if not 1 <= len(a) <= TRIM_ADAPTER_MAX:
+                    raise ValueError(f"Trim: an adapter of {len(a)} bytes (1 to "
+                                     f"{TRIM_ADAPTER_MAX})")
+            mates.append(got)
+        if mates[1] and not mates[0]:
+            raise ValueError("Trim: adapters2 without adapters")
+        if not mates[0] and (vals["min_overlap"] != 3 or vals["max_err_pct"] != 10):
+            raise ValueError("Trim: min_overlap and max_err_pct go with adapters")
+        self.head, self.tail, self.q5, self.q3 = vals["head"], vals["tail"], vals["q5"], vals["q3"]
+        self.min_overlap, self.max_err_pct = vals["min_overlap"], vals["max_err_pct"]
+        self.max_len, self.trim_n = vals["max_len"], bool(trim_n)
+        self.adapters, self.adapters2 = mates
+
+    def spec(self):
+        """(fqz5_trim_spec, fqz5_trim_adapters) as the library takes them
+        (values past a field's range clipped to it: no record is that long)."""
+        t, ad = _TrimSpec(), _TrimAdapters()
+        u32, u64 = (1 << 32) - 1, (1 << 64) - 1
+        if self.head is not None or self.tail is not None:
+            t.set |= 1
+            t.head, t.tail = min(self.head or 0, u64), min(self.tail or 0, u64)
+        if self.q5 is not None:
+            t.set |= 2
+            t.q5 = self.q5
+        if self.q3 is not None:
+            t.set |= 4
+            t.q3 = self.q3
+        if self.adapters:
+            t.set |= 8
+            t.min_overlap, t.max_err_pct = min(self.min_overlap, u32), self.max_err_pct
+            t.n_adapters[0], t.n_adapters[1] = len(self.adapters), len(self.adapters2)
+            for j, a in enumerate(self.adapters + self.adapters2):
+                ad.len[j] = len(a)
+                C.memmove(ad.bytes[j], a, len(a))
+        if self.trim_n:
+            t.set |= 16
+        if self.max_len is not None:
+            t.set |= 32
+            t.max_len = min(self.max_len, u64)
+        return t, ad
+
+    def keys(self) -> tuple:
+        """The sections the cut points are judged on (see above)."""
+        if self.q5 is not None or self.q3 is not None:
+            return (S.SEC_SEQ, S.SEC_QUAL)
+        if self.adapters or self.trim_n:
+            return (S.SEC_SEQ,)
+        return ()
+
+
+class TrimHits:
+    """The result of a trim: `records` (np.uint64) the file record numbers
+    selected (all of them without a Filter), ascending; `total` the units seen
+    (records, with pairs pairs); `failed` (np.uint64[7]) the units the Filter
+    failed, as in FilterHits, judged on the trimmed records; `written` the
+    text bytes written; `bases_in`, `bases_out` the bases before and after
+    trimming; `trimmed[k]`, `removed[k]` (np.uint64[5]) the records step k of
+    STEPS shortened and the bases it took off; `adapter_hits` (np.uint64, one
+    per adapter, adapters2's after adapters') the records each adapter cut:
+    all counted over every record seen, before any selection.  per_record:
+    `starts`, `lengths` (np.uint32) per file record where its kept interval
+    starts and how long it is."""
+    STEPS = ("clip", "quality", "adapter", "trim_n", "crop")
+
+    def __init__(self, records, total: int, failed, counts, n_adapters: int, written: int = 0,
+                 starts=None, lengths=None):
+        self.records, self.total, self.failed, self.written = records, total, failed, written
+        self.bases_in, self.bases_out = int(counts[0]), int(counts[1])
+        self.trimmed, self.removed = counts[2:7].copy(), counts[7:12].copy()
+        self.adapter_hits = counts[12:12 + n_adapters].copy()
+        self.starts, self.lengths = starts, lengths
+
+
+def _trim_host(trim: Trim, seq, qual, lens, pairs: bool = False, compact: bool = False):
+    """fqz5_trim_host of one block: (starts, new lengths, the counts'
+    words[, the compacted bases, the compacted qualities])."""
+    so = _load()
+    lens = np.ascontiguousarray(lens, np.uint32)
+    start, new = np.zeros(len(lens), np.uint32), np.zeros(len(lens), np.uint32)
+    counts = np.zeros(12 + 2 * TRIM_ADAPTERS, np.uint64)
+    total = int(lens.astype(np.uint64).sum())
+    oseq = np.zeros(total + 1, np.uint8) if compact and seq is not None else None
+    oqual = np.zeros(total + 1, np.uint8) if compact and qual is not None else None
+    t, ad = trim.spec()
+    _check(so.fqz5_trim_host(C.byref(t), C.byref(ad), None if seq is None else bytes(seq),
+                             None if qual is None else bytes(qual),
+                             len(seq) if seq is not None else total, lens.ctypes.data, len(lens),
+                             int(pairs), start.ctypes.data, new.ctypes.data, counts.ctypes.data,
+                             None if oseq is None else oseq.ctypes.data,
+                             None if oqual is None else oqual.ctypes.data), "fqz5_trim_host")
+    if not compact:
+        return start, new, counts
+    kept = int(new.astype(np.uint64).sum())
+    return (start, new, counts, None if oseq is None else oseq[:kept].tobytes(),
+            None if oqual is None else oqual[:kept].tobytes())
+
+
+class _TrimBlock:
+    """One block's cuts on the device: `start` (tensor), `new` (the new
+    lengths, host), and the streams compacted so far (`ptr` by section; the
+    tensors in `held` live as long as the block's addresses do)."""
+
+    def __init__(self, start, new):
+        self.start, self.new, self.total = start, new, int(new.astype(np.uint64).sum())
+        self.ptr, self.held = {}, []
+
+    def gather(self, so, sec, src: int, seq_ulen: int, ln, device) -> None:
+        import torch
+        dst = torch.empty(self.total + 1, dtype=torch.uint8, device=device)
+        got = C.c_uint64(0)
+        _check(so.fqz5_trim_gather(src, seq_ulen, ln.ctypes.data, self.start.data_ptr(),
+                                   self.new.ctypes.data, len(ln), dst.data_ptr(), self.total,
+                                   C.byref(got)), "fqz5_trim_gather")
+        self.held.append(dst)
+        self.ptr[sec] = dst.data_ptr()
+
+
+def _trim(rd, trim: Trim, flt, pairs, invert, extract, per_record, plus_name, with_qual, device,
+          window_bytes, sink) -> TrimHits:
+    """The trim over `rd`; sink(windows of texts) consumes the selected
+    records' text (extract) and returns the bytes written."""
+    import torch
+    if not isinstance(trim, Trim):
+        raise TypeError("the steps are a Trim")
+    if flt is not None and not isinstance(flt, Filter):
+        raise TypeError("the criteria are a Filter")
+    so = _load()
+    (tspec, tad), fspec = trim.spec(), (flt or Filter()).spec()
+    tkeys, fkeys = trim.keys(), (flt.keys() if flt is not None else ())
+    keys = max(tkeys, fkeys, key=len)             # (each a prefix of (SEC_SEQ, SEC_QUAL))
+    failed, total = np.zeros(7, np.uint64), [0]
+    counts = np.zeros(12 + 2 * TRIM_ADAPTERS, np.uint64)
+    starts, lengths = [], []
+
+    def match(ptr, v, ln, hits):
+        start = torch.empty(max(len(ln), 1), dtype=torch.int32, device=device)
+        new = np.zeros(len(ln), np.uint32)
+        _check(so.fqz5_trim_cuts(C.byref(tspec), C.byref(tad),
+                                 ptr.get(S.SEC_SEQ) if S.SEC_SEQ in tkeys else None,
+                                 ptr.get(S.SEC_QUAL) if S.SEC_QUAL in tkeys else None,
+                                 v.seq_ulen, ln.ctypes.data, len(ln), int(pairs), start.data_ptr(),
+                                 new.ctypes.data, counts.ctypes.data), "fqz5_trim_cuts")
+        blk = ptr["trim"] = _TrimBlock(start, new)
+        for sec in keys if extract else fkeys:    # (the streams the filter or the text needs)
+            blk.gather(so, sec, ptr[sec], v.seq_ulen, ln, device)
+        n = C.c_uint64(0)
+        _check(so.fqz5_filter_match(C.byref(fspec), blk.ptr.get(S.SEC_SEQ),
+                                    blk.ptr.get(S.SEC_QUAL), blk.total, new.ctypes.data, len(ln),
+                                    int(pairs), int(invert), hits[0].data_ptr(), C.byref(n),
+                                    failed.ctypes.data, None), "fqz5_filter_match")
+        total[0] += len(ln) // (2 if pairs else 1)
+        if per_record:
+            starts.append(start[:len(ln)].cpu().numpy().view(np.uint32))
+            lengths.append(new)
+        return int(n.value)
+
+    def hook(ptr, v, ln):
+        blk = ptr["trim"]
+        for sec in (S.SEC_SEQ, S.SEC_QUAL):       # those decoded after the match
+            if sec in ptr and sec not in blk.ptr:
+                blk.gather(so, sec, ptr[sec], v.seq_ulen, ln, device)
+        ptr.update(blk.ptr)
+        return blk.new
+    recs, _, written = _lookup(rd, keys, ("keys", "trim"), match, pairs, extract, plus_name,
+                               with_qual, device, window_bytes, sink, hook)
+    cat = lambda xs: np.concatenate(xs) if xs else np.zeros(0, np.uint32)   # noqa: E731
+    return TrimHits(np.asarray(recs, np.uint64), total[0], failed, counts,
+                    len(trim.adapters) + len(trim.adapters2), written,
+                    cat(starts) if per_record else None, cat(lengths) if per_record else None)
+
+
+def trim_records(src, trim: Trim, flt: Filter | None = None, pairs: bool = False,
+                 per_record: bool = False, device: str = "cuda",
+                 window_bytes: int | None = None) -> TrimHits:
+    """The cuts `trim` makes in the records of a .fqz5 (a path, the file's
+    bytes, or a positioned reader), found on the GPU (see above), and the
+    records whose trimmed form passes `flt` (all without one): every block is
+    read, checked and CRC-checked; only the sections the steps and the
+    criteria need are decoded (none for clip and crop alone) and no name
+    section; nothing is written.  pairs: records 2k and 2k + 1 are mates, each
+    trimmed on its own (the odd ones with adapters2), kept only when both pass
+    `flt`.  A quality cutoff on a block without qualities is an error."""
+    return _run(_reader(src), "trim_records", lambda rd: _trim(
+        rd, trim, flt, pairs, False, False, per_record, False, True, device, window_bytes, None))
+
+
+def trim_bytes(data, trim: Trim, flt: Filter | None = None, plus_name: bool = False,
+               with_qual: bool = True, device: str = "cuda") -> bytes:
+    """The records of a .fqz5 held in memory, trimmed, those that then pass
+    `flt`, in file order, as FASTQ text (with_qual False: FASTA text).  A
+    Trim() with nothing set and no Filter gives decompress_bytes' text.  See
+    trim_records."""
+    out = []
+    _trim(_PosBytes(data), trim, flt, False, False, True, False, plus_name, with_qual, device, None,
+          _bytes_sink(out))
+    _trace_dump("trim")
+    return b"".join(out)
+
+
+def trim_file(src: str, dst: str, trim: Trim, flt: Filter | None = None, plus_name: bool = False,
+              dst2: str | None = None, with_qual: bool = True, invert: bool = False,
+              window_bytes: int | None = None, device: str = "cuda") -> TrimHits:
+    """The records of the .fqz5 file src, trimmed, to dst in file order: one
+    pass over the file in windows of at most `window_bytes` of compressed
+    data, as filter_file makes it, the cut points found and the streams
+    compacted on the GPU before the Filter judges them and the text is laid
+    out.  flt: only the records whose trimmed form passes are written (invert:
+    those that do not).  dst2: the records are interleaved pairs, each mate
+    trimmed on its own (the odd ones with adapters2), a pair kept only when
+    both trimmed mates pass, R1 records to dst and R2 records to dst2.
+    with_qual False: the text is FASTA.  A ".gz" destination is
+    gzip-compressed.  One process; returns the TrimHits."""
+    outs = [dst] + ([dst2] if dst2 is not None else [])
+    return _run((_PosFile(src), True), "trim", lambda rd: _trim(
+        rd, trim, flt, dst2 is not None, invert, True, False, plus_name, with_qual, device,
+        window_bytes, lambda w: sum(_write_texts(outs, w))))

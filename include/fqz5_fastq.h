@@ -40,6 +40,11 @@
  *                       length, N count, mean quality, low-quality share, GC
  *                       share and complexity pass a rule, picked on the
  *                       device (fqz5file.filter_records / filter_file).
+ *   fqz5_trim_*         trim and clip: per record the interval of its bases
+ *                       and qualities kept after the clip, quality, adapter,
+ *                       N and crop steps, found on the device, and the
+ *                       streams compacted to it (fqz5file.trim_records /
+ *                       trim_file).
  *
  * Offsets are bytes into the text.  Calls return 0 (fqz5_fastq_index: 1 for
  * FASTA text; fqz5_fastq_blocks: the block count) or -1 with
@@ -362,6 +367,109 @@ int fqz5_filter_match(const fqz5_filter_spec *, const uint8_t *d_seq, const uint
 int fqz5_filter_host(const fqz5_filter_spec *, const uint8_t *seq, const uint8_t *qual,
                      uint64_t seq_len, const uint32_t *lens, uint64_t nrec, int pairs, int invert,
                      uint8_t *keep, uint64_t *failed, const fqz5_filter_sums *sums);
+
+/* Trim and clip (trim.hip; fqz5file.trim_records / trim_file): per record the
+ * interval of its bases and qualities that is kept, the cut points found on
+ * the device, and the streams compacted to those intervals, after which they
+ * are ordinary streams with new lengths (fqz5_filter_match judges them,
+ * fqz5_fastq_format_list lays out their text).  Names are never trimmed.
+ *
+ * The rule is exact integer arithmetic, and the device and fqz5_trim_host
+ * agree bit for bit.  A record has L bases s[0..L) and qualities q[0..L) (q
+ * the quality line's byte - 33, as the decoder leaves it).  Its kept interval
+ * [a, b) starts as [0, L) and goes through five steps in this order; a step
+ * whose bit (below) is not in `set` does nothing, and every step leaves
+ * a <= b:
+ *   0 clip     a = min(head, L); b = max(a, L - min(tail, L))
+ *   1 quality  both ends are judged on the interval [a0, b0) step 0 left,
+ *              independently, by the running-sum rule of BWA and cutadapt:
+ *                3' end (cutoff q3): sum = 0, best = 0, stop = b0; for
+ *                i = b0 - 1 down to a0: sum += q3 - q[i]; if sum < 0 the scan
+ *                ends; if sum > best (strictly: a tie keeps the larger i):
+ *                best = sum, stop = i
+ *                5' end (cutoff q5): start = a0; for i = a0 upwards:
+ *                sum += q5 - q[i]; sum < 0 ends the scan; sum > best:
+ *                best = sum, start = i + 1
+ *              (an end whose cutoff is not set: start = a0, stop = b0); then
+ *              a = start, b = max(start, stop).  Sums are i64.
+ *   2 adapter  the smallest p in [a, b - min_overlap] at which some adapter
+ *              matches; then b = p.  Adapter A of m bytes matches at p when,
+ *              with ov = min(m, b - p), ov >= min_overlap and the positions
+ *              0 <= k < ov with s[p + k] != A[k] number at most
+ *              (max_err_pct * ov) / 100 (integer division).  Bytes are
+ *              compared as they are: no case folding, no wildcard.  Of several
+ *              adapters that match at the smallest p the lowest index counts.
+ *   3 trim_n   while a < b and s[a] is in "Nn": a++; while b > a and s[b - 1]
+ *              is in "Nn": b--
+ *   4 crop     b = min(b, a + max_len)
+ * With pairs, records 2k and 2k + 1 are each trimmed on their own; the odd
+ * ones take the mate-2 adapters when there are any, else mate 1's.
+ *
+ * Counts (u64 words, added to): [0] bases_in, [1] bases_out, the bases of all
+ * records before and after; [2 + k] trimmed[k], the records step k shortened;
+ * [7 + k] removed[k], the bases step k took off; [12 + j] adapter_hits[j], the
+ * records cut by the adapter in slot j. */
+#define FQZ5_TRIM_STEPS 5
+#define FQZ5_TRIM_ADAPTERS 16                 /* per mate */
+#define FQZ5_TRIM_ADAPTER_MAX 128             /* bytes of one adapter */
+#define FQZ5_TRIM_COUNTS (12 + 2 * FQZ5_TRIM_ADAPTERS)
+#define FQZ5_TRIM_CLIP 1u
+#define FQZ5_TRIM_Q5 2u
+#define FQZ5_TRIM_Q3 4u
+#define FQZ5_TRIM_ADAPTER 8u
+#define FQZ5_TRIM_N 16u
+#define FQZ5_TRIM_CROP 32u
+typedef struct {
+    uint32_t set;                 /* the FQZ5_TRIM_ bits of the steps that count */
+    uint32_t q5, q3;              /* cutoffs, at most 93 */
+    uint32_t min_overlap, max_err_pct;        /* >= 1; <= 100 */
+    uint32_t n_adapters[2];       /* mate 1's, mate 2's (0: mate 1's serve both) */
+    uint64_t head, tail, max_len;
+} fqz5_trim_spec;
+
+/* the adapters: mate 1's in slots 0 .. n_adapters[0] - 1, mate 2's after them;
+ * each 1 .. FQZ5_TRIM_ADAPTER_MAX bytes */
+typedef struct {
+    uint32_t len[2 * FQZ5_TRIM_ADAPTERS];
+    uint8_t bytes[2 * FQZ5_TRIM_ADAPTERS][FQZ5_TRIM_ADAPTER_MAX];
+} fqz5_trim_adapters;
+
+/* d_seq[0..seq_len) and d_qual[0..seq_len) (device) hold nrec records whose
+ * lengths are h_len (host).  Per record its kept interval: where it starts
+ * within the record into d_start (device, nrec words; stays there for
+ * fqz5_trim_gather) and its length into h_new_len (host, nrec words); the
+ * counts are added to h_counts (host, FQZ5_TRIM_COUNTS words).  `adapters` is
+ * read only with the adapter step.  A stream that no step that is set reads
+ * (the quality step: d_qual; adapter and trim_n: d_seq) is not read and may be
+ * NULL.  Fails, before anything is written: a step without its stream, a
+ * spec outside the limits above, lengths that do not sum to seq_len,
+ * nrec >= 2^31, an odd nrec with pairs.  nrec 0: nothing is written. */
+int fqz5_trim_cuts(const fqz5_trim_spec *, const fqz5_trim_adapters *adapters,
+                   const uint8_t *d_seq, const uint8_t *d_qual, uint64_t seq_len,
+                   const uint32_t *h_len, uint64_t nrec, int pairs, uint32_t *d_start,
+                   uint32_t *h_new_len, uint64_t *h_counts);
+
+/* One stream compacted: bytes [start, start + new_len) of every record of
+ * d_src[0..seq_len) (device; record lengths h_len) one after the other into
+ * d_dst (device, dst_cap bytes), *out_len their number.  d_start: device,
+ * h_new_len: host, as fqz5_trim_cuts leaves them.  Source and destination are
+ * distinct buffers: ranges that overlap fail, as do an interval outside its
+ * record, lengths that do not sum to seq_len and a result above dst_cap
+ * (h_new_len is checked against h_len on the host; d_start + new_len is
+ * clipped to the record on the device, so no byte outside [0, seq_len) is
+ * read). */
+int fqz5_trim_gather(const uint8_t *d_src, uint64_t seq_len, const uint32_t *h_len,
+                     const uint32_t *d_start, const uint32_t *h_new_len, uint64_t nrec,
+                     uint8_t *d_dst, uint64_t dst_cap, uint64_t *out_len);
+
+/* Host restatement of the rule, one thread, no GPU: start and new_len (nrec
+ * words each), counts as above (added to), and, where given, the compacted
+ * bases into out_seq and qualities into out_qual (the sum of new_len bytes
+ * each; may be NULL).  Fails as fqz5_trim_cuts does. */
+int fqz5_trim_host(const fqz5_trim_spec *, const fqz5_trim_adapters *adapters,
+                   const uint8_t *seq, const uint8_t *qual, uint64_t seq_len,
+                   const uint32_t *lens, uint64_t nrec, int pairs, uint32_t *start,
+                   uint32_t *new_len, uint64_t *counts, uint8_t *out_seq, uint8_t *out_qual);
 
 #ifdef __cplusplus
 }
