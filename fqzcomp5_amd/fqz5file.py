@@ -193,6 +193,42 @@ def _load():
         so.fqz5_trim_host.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint64,
                                       C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p]
+        so.fqz5_dedup_table_bytes.restype = C.c_uint64
+        so.fqz5_dedup_table_bytes.argtypes = [C.c_uint64]
+        so.fqz5_dedup_table_new.restype = C.c_void_p
+        so.fqz5_dedup_table_new.argtypes = [C.c_uint64]
+        so.fqz5_dedup_table_free.restype = None
+        so.fqz5_dedup_table_free.argtypes = [C.c_void_p]
+        so.fqz5_dedup_table_slots.restype = C.c_uint64
+        so.fqz5_dedup_table_slots.argtypes = [C.c_void_p]
+        so.fqz5_dedup_table_reset.restype = C.c_int
+        so.fqz5_dedup_table_reset.argtypes = [C.c_void_p]
+        so.fqz5_dedup_table_slot.restype = C.c_int
+        so.fqz5_dedup_table_slot.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+        so.fqz5_dedup_keys.restype = C.c_int
+        so.fqz5_dedup_keys.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int,
+                                       C.c_int, C.c_void_p]
+        so.fqz5_dedup_insert_keys.restype = C.c_int
+        so.fqz5_dedup_insert_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+                                              C.c_void_p]
+        so.fqz5_dedup_match.restype = C.c_int
+        so.fqz5_dedup_match.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                        C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p,
+                                        C.POINTER(C.c_uint64), C.c_void_p]
+        so.fqz5_dedup_levels.restype = C.c_int
+        so.fqz5_dedup_levels.argtypes = [C.c_void_p, C.c_void_p]
+        so.fqz5_dedup_keys_host.restype = C.c_int
+        so.fqz5_dedup_keys_host.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int,
+                                            C.c_int, C.c_void_p]
+        so.fqz5_dedup_host_new.restype = C.c_void_p
+        so.fqz5_dedup_host_new.argtypes = []
+        so.fqz5_dedup_host_free.restype = None
+        so.fqz5_dedup_host_free.argtypes = [C.c_void_p]
+        so.fqz5_dedup_host_add.restype = C.c_int
+        so.fqz5_dedup_host_add.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int,
+                                           C.c_void_p, C.c_void_p]
+        so.fqz5_dedup_host_levels.restype = C.c_int
+        so.fqz5_dedup_host_levels.argtypes = [C.c_void_p, C.c_void_p]
         _bound = True
     return so
 
@@ -212,7 +248,10 @@ def _load():
 # section), filter (the sums and pick kernels), decode, format, download,
 # write; trim_records / trim_file: the same with trim, the cuts, the key
 # streams' compaction and the filter's kernels, in place of filter, and the
-# remaining streams' compaction inside format);
+# remaining streams' compaction inside format); dedup_records / dedup_file /
+# duplication: the filter's with table, the device table made, after index,
+# dedup (the key, insert and pick kernels) in place of filter, and for
+# duplication levels, the pass over the table, at the end);
 # the stages end with what the library synchronises
 _TRACE = {}
 
@@ -3329,3 +3368,228 @@ def trim_file(src: str, dst: str, trim: Trim, flt: Filter | None = None, plus_na
     return _run((_PosFile(src), True), "trim", lambda rd: _trim(
         rd, trim, flt, dst2 is not None, invert, True, False, plus_name, with_qual, device,
         window_bytes, lambda w: sum(_write_texts(outs, w))))
+
+
+# ---------------------------------------------------------------------------
+# Duplicates
+#
+# "Drop the reads seen before" (fastp --dedup, seqkit rmdup -s, clumpify
+# dedupe): the pass of the filter with the sequence section as the only key,
+# and the first record pass whose verdict depends on every earlier record of
+# the file.  A unit (a record, with pairs the records 2k and 2k + 1) is kept
+# when no earlier unit has the same key; the key is 128 bits summed from the
+# unit's bases on the device, so two units are duplicates when their keys are
+# equal: equal sequences always, unequal ones with probability about 2^-128 per
+# pair (include/fqz5_fastq.h).  A device table with at least twice the file's
+# units in slots (the unit count comes from the block index) lives across
+# blocks and windows; per block fqz5_dedup_match (dedup.hip) sums the keys,
+# inserts them wait-free under the units' file numbers and selects the units
+# whose number is their key's smallest.  _key_windows hands blocks over in file
+# order, so every earlier unit is in the table when a block is judged and
+# "keep the first occurrence" needs no second pass.  No name section is decoded
+# before the hits' text is laid out, and no quality section for a block whose
+# records are all duplicates.  One process.  Not built: deduplication after a
+# Trim or Filter in the same pass, keys that include the qualities or a UMI
+# from the name, mismatch-tolerant duplicates, the most duplicated sequences
+# themselves, several ranks.
+# ---------------------------------------------------------------------------
+DEDUP_LEVELS = 1025
+DEDUP_TABLE_SHARE = 0.5                         # of the device's free memory: max_table_bytes
+
+
+class DedupHits:
+    """The result of a deduplication: `records` (np.uint64) the file record
+    numbers selected, ascending (pairs: both mates); `total` the units seen
+    (records, with pairs pairs); `distinct` the different keys among them (the
+    units kept without invert); `written` the text bytes written; `first`
+    (np.uint64, per_record) for every unit the file record number of the first
+    unit with its key (pairs: of that unit's first mate)."""
+
+    def __init__(self, records, total: int, distinct: int, written: int = 0, first=None):
+        self.records, self.total, self.distinct = records, total, distinct
+        self.written, self.first = written, first
+
+
+class Duplication:
+    """Duplication levels of a whole file, exact (every unit counted, not an
+    estimate from the first 100 000 reads as FastQC's): `total` the units,
+    `distinct` the different keys, `levels` (np.uint64[1025]) at c the keys
+    that c units carry for c < 1024 and at 1024 those that 1024 and more
+    carry, `max_count` the most units one key has, `remaining` the share of
+    units left after deduplication (distinct / total; 1.0 for no units)."""
+
+    def __init__(self, total: int, distinct: int, levels, max_count: int):
+        self.total, self.distinct, self.levels, self.max_count = total, distinct, levels, max_count
+        self.remaining = distinct / total if total else 1.0
+
+
+class _DedupTable(_Native):
+    """fqz5_dedup_table for `units` units on the device (freed on exit)."""
+    FREE = "fqz5_dedup_table_free"
+
+    def __init__(self, units: int):
+        self.so = _load()
+        self.p = self.so.fqz5_dedup_table_new(units)
+        if not self.p:
+            raise _lib.NativeError("fqz5_dedup_table_new: " + _lib.last_error())
+
+    def levels(self) -> np.ndarray:
+        out = np.zeros(DEDUP_LEVELS + 2, np.uint64)
+        _check(self.so.fqz5_dedup_levels(self.p, out.ctypes.data), "fqz5_dedup_levels")
+        return out
+
+
+class _DedupHostTable(_Native):
+    """fqz5_dedup_host_table (freed on exit)."""
+    FREE = "fqz5_dedup_host_free"
+
+    def __init__(self):
+        self.so = _load()
+        self.p = self.so.fqz5_dedup_host_new()
+        if not self.p:
+            raise _lib.NativeError("fqz5_dedup_host_new: " + _lib.last_error())
+
+    def levels(self) -> np.ndarray:
+        out = np.zeros(DEDUP_LEVELS + 2, np.uint64)
+        _check(self.so.fqz5_dedup_host_levels(self.p, out.ctypes.data), "fqz5_dedup_host_levels")
+        return out
+
+
+def _dedup_host(seq, lens, pairs: bool = False, revcomp: bool = False, invert: bool = False,
+                table: _DedupHostTable | None = None, first_unit: int = 0):
+    """fqz5_dedup_keys_host of one block and fqz5_dedup_host_add of its keys
+    as the units first_unit .. into `table` (None: a table of its own): (the
+    keys, np.uint64[units, 2]; keep per unit; per unit the first unit with its
+    key)."""
+    import contextlib
+    so = _load()
+    lens = np.ascontiguousarray(lens, np.uint32)
+    seq = bytes(seq)
+    units = len(lens) // (2 if pairs else 1)
+    keys = np.zeros((units, 2), np.uint64)
+    _check(so.fqz5_dedup_keys_host(seq, len(seq), lens.ctypes.data, len(lens), int(pairs),
+                                   int(revcomp), keys.ctypes.data), "fqz5_dedup_keys_host")
+    keep, first = np.zeros(units, np.uint8), np.zeros(units, np.uint64)
+    with (_DedupHostTable() if table is None else contextlib.nullcontext(table)) as t:
+        _check(so.fqz5_dedup_host_add(t.p, keys.ctypes.data, units, first_unit, int(invert),
+                                      keep.ctypes.data, first.ctypes.data), "fqz5_dedup_host_add")
+    return keys, keep, first
+
+
+def _dedup(rd, pairs, revcomp, invert, extract, per_record, plus_name, with_qual, device,
+           window_bytes, sink, max_table_bytes=None, levels: bool = False):
+    """The deduplication over `rd`; sink(windows of texts) consumes the
+    selected records' text (extract) and returns the bytes written.  Returns
+    the DedupHits, with `levels` (the pass over the table after the last
+    block) the pair (DedupHits, fqz5_dedup_levels' words)."""
+    import torch
+    so = _load()
+    mates = 2 if pairs else 1
+    with _stage("index"):
+        units = sum(int(n) // mates for _, _, n in read_index(rd))
+    need = int(so.fqz5_dedup_table_bytes(units))
+    if max_table_bytes is None:
+        max_table_bytes = int(DEDUP_TABLE_SHARE * torch.cuda.mem_get_info(device)[0])
+    if not need or need > max_table_bytes:
+        raise _lib.NativeError(f"dedup: a table of {need or 'more than 2^36'} bytes for {units} "
+                               f"units exceeds max_table_bytes = {max_table_bytes}")
+    with _stage("table"):
+        tab = _DedupTable(units)
+    with tab:
+        unit0, first = [0], []
+
+        def match(ptr, v, ln, hits):
+            n, k = C.c_uint64(0), len(ln) // mates
+            d_first = torch.empty(max(k, 1), dtype=torch.int64, device=device) if per_record else None
+            _lib.after_torch(device)
+            _check(so.fqz5_dedup_match(tab.p, ptr[S.SEC_SEQ], v.seq_ulen, ln.ctypes.data, len(ln),
+                                       int(pairs), int(revcomp), int(invert), unit0[0],
+                                       hits[0].data_ptr(), C.byref(n),
+                                       d_first.data_ptr() if per_record else None),
+                   "fqz5_dedup_match")
+            unit0[0] += k
+            if per_record:
+                first.append(d_first[:k].cpu().numpy().view(np.uint64) * np.uint64(mates))
+            return int(n.value)
+        recs, _, written = _lookup(rd, (S.SEC_SEQ,), ("keys", "dedup"), match, pairs, extract,
+                                   plus_name, with_qual, device, window_bytes, sink)
+        total, picked = unit0[0], len(recs) // mates
+        hits = DedupHits(np.asarray(recs, np.uint64), total, total - picked if invert else picked,
+                         written, (np.concatenate(first) if first else np.zeros(0, np.uint64))
+                         if per_record else None)
+        if not levels:
+            return hits
+        with _stage("levels"):
+            return hits, tab.levels()
+
+
+def dedup_records(src, pairs: bool = False, revcomp: bool = False, invert: bool = False,
+                  per_record: bool = False, device: str = "cuda",
+                  window_bytes: int | None = None, max_table_bytes: int | None = None) -> DedupHits:
+    """The records of a .fqz5 (a path, the file's bytes, or a positioned
+    reader) that are the first of their sequence in the file, judged on the
+    GPU (see above): every block is read, checked and CRC-checked, its
+    sequence section alone decoded.  Two units are duplicates when their
+    128-bit keys are equal: equal sequences always (bytes as they are, no case
+    folding), unequal ones with probability about 2^-128 per pair.  pairs:
+    records 2k and 2k + 1 are one unit, a duplicate when both mates are (a
+    block with an odd record count is an error).  revcomp: a sequence and its
+    reverse complement are the same; with pairs, a pair and the pair with its
+    mates swapped (no base is complemented).  invert: exactly the units that
+    are not the first.  per_record: `first` per unit.  max_table_bytes: the
+    most device memory the table may take (default: half of what is free); a
+    table beyond it is an error that names the size."""
+    return _run(_reader(src), "dedup_records", lambda rd: _dedup(
+        rd, pairs, revcomp, invert, False, per_record, False, True, device, window_bytes, None,
+        max_table_bytes))
+
+
+def dedup_bytes(data, revcomp: bool = False, invert: bool = False, plus_name: bool = False,
+                with_qual: bool = True, device: str = "cuda", window_bytes: int | None = None,
+                max_table_bytes: int | None = None) -> bytes:
+    """The records of a .fqz5 held in memory that are the first of their
+    sequence, in file order, as the text decompress_bytes gives for them
+    (with_qual False: FASTA text).  See dedup_records."""
+    out = []
+    _dedup(_PosBytes(data), False, revcomp, invert, True, False, plus_name, with_qual, device,
+           window_bytes, _bytes_sink(out), max_table_bytes)
+    _trace_dump("dedup")
+    return b"".join(out)
+
+
+def dedup_file(src: str, dst: str, dst2: str | None = None, with_qual: bool = True,
+               plus_name: bool = False, revcomp: bool = False, invert: bool = False,
+               device: str = "cuda", window_bytes: int | None = None,
+               max_table_bytes: int | None = None) -> DedupHits:
+    """The records of the .fqz5 file src that are the first of their sequence
+    to dst, in file order: one pass over the file in windows of at most
+    `window_bytes` of compressed data; every block is read once, checked
+    against its index entry and CRC-checked, its sequence section decoded and
+    judged on the GPU against a table of every earlier unit; the name and
+    quality sections are decoded for the blocks with selected records only,
+    and their text is laid out on the GPU (fqz5_fastq_format_list).  dst2: the
+    records are interleaved pairs, a pair is one unit, R1 records to dst and R2
+    records to dst2.  with_qual False: the text is FASTA and no quality
+    section is decoded.  invert: the duplicates instead.  A ".gz" destination
+    is gzip-compressed.  One process; returns the DedupHits (`written`: the
+    text bytes written).  See dedup_records."""
+    outs = [dst] + ([dst2] if dst2 is not None else [])
+    return _run((_PosFile(src), True), "dedup", lambda rd: _dedup(
+        rd, dst2 is not None, revcomp, invert, True, False, plus_name, with_qual, device,
+        window_bytes, lambda w: sum(_write_texts(outs, w)), max_table_bytes))
+
+
+def duplication(src, pairs: bool = False, revcomp: bool = False, device: str = "cuda",
+                window_bytes: int | None = None,
+                max_table_bytes: int | None = None) -> Duplication:
+    """The duplication levels of a .fqz5 (a path, the file's bytes, or a
+    positioned reader): the pass of dedup_records with nothing extracted, then
+    one pass over the table on the GPU.  Exact over the whole file, every unit
+    counted: not FastQC's estimate from the first 100 000 reads.  See
+    Duplication and dedup_records."""
+    def run(rd):
+        h, lv = _dedup(rd, pairs, revcomp, False, False, False, False, True, device, window_bytes,
+                       None, max_table_bytes, levels=True)
+        return Duplication(h.total, int(lv[DEDUP_LEVELS]), lv[:DEDUP_LEVELS].copy(),
+                           int(lv[DEDUP_LEVELS + 1]))
+    return _run(_reader(src), "duplication", run)

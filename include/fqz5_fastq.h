@@ -45,6 +45,10 @@
  *                       N and crop steps, found on the device, and the
  *                       streams compacted to it (fqz5file.trim_records /
  *                       trim_file).
+ *   fqz5_dedup_*        duplicates: per unit a 128-bit key of its bases summed
+ *                       on the device, and a device table over the whole file
+ *                       that keeps each key's first unit and count
+ *                       (fqz5file.dedup_records / dedup_file / duplication).
  *
  * Offsets are bytes into the text.  Calls return 0 (fqz5_fastq_index: 1 for
  * FASTA text; fqz5_fastq_blocks: the block count) or -1 with
@@ -470,6 +474,101 @@ int fqz5_trim_host(const fqz5_trim_spec *, const fqz5_trim_adapters *adapters,
                    const uint8_t *seq, const uint8_t *qual, uint64_t seq_len,
                    const uint32_t *lens, uint64_t nrec, int pairs, uint32_t *start,
                    uint32_t *new_len, uint64_t *counts, uint8_t *out_seq, uint8_t *out_qual);
+
+/* Duplicates (dedup.hip; fqz5file.dedup_records / dedup_file / duplication):
+ * which records of a file are the first of their sequence.  A unit is one
+ * record, with pairs the records 2k and 2k + 1 of a block.  A unit is kept
+ * when no earlier unit of the file has the same key; invert selects exactly
+ * the others.  Two units are duplicates when their 128-bit keys are equal:
+ * equal sequences always, unequal sequences with probability about 2^-128 per
+ * pair of units.
+ *
+ * A unit's key is a pair of u64 words, each a sum mod 2^64 of one term per
+ * (position, byte) of its bases and one term for its length, so a record
+ * spread over several tiles is summed tile by tile, in any order, to the same
+ * bits; the device, fqz5_dedup_keys_host and tests/dedup_ref.py agree bit for
+ * bit.  With
+ *     mix(x):  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27;
+ *              x *= 0x94D049BB133111EB; x ^= x >> 31          (all u64)
+ *     K_s(rec) = mix(SEED_s ^ L) + sum over i of mix(SEED_s + (i << 8 | c_i))
+ * (L the record's length, c_i its i-th byte as it is: no case folding) and
+ * the four odd seeds below:
+ *     a record                  (K_0, K_1)
+ *     pairs                     (K_0(R1) + K_2(R2), K_1(R1) + K_3(R2))
+ *     revcomp                   the smaller of the record's key and its reverse
+ *                               complement's, compared first word, then second;
+ *                               the reverse complement's sums have
+ *                               mix(SEED_s + ((L - 1 - i) << 8 | comp(c_i))) for
+ *                               byte i, comp swapping A<->T and C<->G in either
+ *                               case and leaving every other byte alone
+ *     revcomp with pairs        the smaller of key(R1, R2) and key(R2, R1); no
+ *                               base is complemented (the other strand of a
+ *                               fragment shows up as swapped mates)
+ *
+ * The table: open addressing, linear probing from home slot
+ * (first word) & (slots - 1), slots a power of two >= max(8, 2 * units).  A
+ * slot holds one key, the smallest unit number that carried it (`first`) and
+ * how many units did (`count`, u32).  Inserting is wait-free: no lane waits
+ * for another's store.  Every key word is a legal key word, zero and all ones
+ * included (an empty slot is told apart by bits of its own).  Unit numbers are
+ * the caller's (first_unit + the unit's index in the call); a file's blocks
+ * are given in file order, so `first` is final once the block is judged. */
+#define FQZ5_DEDUP_SEED0 0x9E3779B97F4A7C15ull
+#define FQZ5_DEDUP_SEED1 0xC2B2AE3D27D4EB4Full
+#define FQZ5_DEDUP_SEED2 0x165667B19E3779F9ull
+#define FQZ5_DEDUP_SEED3 0xD6E8FEB86659FD93ull
+#define FQZ5_DEDUP_LEVELS 1025                /* counts 0..1023, then 1024 and more */
+#define FQZ5_DEDUP_LEVEL_WORDS (FQZ5_DEDUP_LEVELS + 2)
+typedef struct fqz5_dedup_table fqz5_dedup_table;
+typedef struct fqz5_dedup_host_table fqz5_dedup_host_table;
+
+/* the device bytes of a table for `units` units (0: more than 2^31 slots) */
+uint64_t fqz5_dedup_table_bytes(uint64_t units);
+/* A new, empty table for `units` units (NULL with fqz5_last_error() set: more
+ * than 2^31 slots, no memory); its slots; emptied again. */
+fqz5_dedup_table *fqz5_dedup_table_new(uint64_t units);
+void fqz5_dedup_table_free(fqz5_dedup_table *);
+uint64_t fqz5_dedup_table_slots(const fqz5_dedup_table *);
+int fqz5_dedup_table_reset(fqz5_dedup_table *);
+/* one slot as it stands: out[0..4) = key words, first, count (count 0: empty) */
+int fqz5_dedup_table_slot(const fqz5_dedup_table *, uint64_t slot, uint64_t *out);
+
+/* The unit keys of a block: d_seq[0..seq_len) (device) holds nrec records
+ * whose lengths are h_len (host); unit u's key goes to d_keys[2u], [2u + 1]
+ * (device, 2 * units words).  Fails, before anything is written: lengths that
+ * do not sum to seq_len, nrec >= 2^31, an odd nrec with pairs. */
+int fqz5_dedup_keys(const uint8_t *d_seq, uint64_t seq_len, const uint32_t *h_len, uint64_t nrec,
+                    int pairs, int revcomp, uint64_t *d_keys);
+/* n keys (device, as above) inserted as the units first_unit ..; d_slot
+ * (device, n words) receives each one's slot.  Fails with "table full" when a
+ * key finds no slot within `slots` probes (the table then holds some of the
+ * call's keys: reset it). */
+int fqz5_dedup_insert_keys(fqz5_dedup_table *, const uint64_t *d_keys, uint64_t n,
+                           uint64_t first_unit, uint32_t *d_slot);
+/* One block: its keys, their insertion as units first_unit .., and the
+ * selected records' indices, ascending, into d_rec (device, nrec entries; both
+ * mates of a selected pair), *n_hit their number.  d_first (device, one u64
+ * per unit, may be NULL): the number of the first unit with the unit's key.
+ * Fails as fqz5_dedup_keys and fqz5_dedup_insert_keys do. */
+int fqz5_dedup_match(fqz5_dedup_table *, const uint8_t *d_seq, uint64_t seq_len,
+                     const uint32_t *h_len, uint64_t nrec, int pairs, int revcomp, int invert,
+                     uint64_t first_unit, uint32_t *d_rec, uint64_t *n_hit, uint64_t *d_first);
+/* The table's duplication levels into h_out (host, FQZ5_DEDUP_LEVEL_WORDS
+ * words): [c] the keys carried by c units for c < 1024, [1024] those carried by
+ * 1024 and more, [1025] the keys, [1026] the largest count. */
+int fqz5_dedup_levels(const fqz5_dedup_table *, uint64_t *h_out);
+
+/* Host restatement, one thread, no GPU: the keys (2 * units words), and a
+ * table (std::unordered_map on the 128-bit key) that takes n keys as the units
+ * first_unit .. and leaves keep[u] (n bytes, may be NULL) = 1 where unit u is
+ * selected and first[u] (n words, may be NULL); its levels as above. */
+int fqz5_dedup_keys_host(const uint8_t *seq, uint64_t seq_len, const uint32_t *lens, uint64_t nrec,
+                         int pairs, int revcomp, uint64_t *keys);
+fqz5_dedup_host_table *fqz5_dedup_host_new(void);
+void fqz5_dedup_host_free(fqz5_dedup_host_table *);
+int fqz5_dedup_host_add(fqz5_dedup_host_table *, const uint64_t *keys, uint64_t n,
+                        uint64_t first_unit, int invert, uint8_t *keep, uint64_t *first);
+int fqz5_dedup_host_levels(const fqz5_dedup_host_table *, uint64_t *out);
 
 #ifdef __cplusplus
 }
