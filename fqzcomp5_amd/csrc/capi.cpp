@@ -234,6 +234,15 @@ int host_encode_mode() {
     return v;
 }
 
+static std::atomic<uint64_t> g_x32_min{host::CHAIN_MIN};
+uint64_t x32_group_min() {
+    static const bool off = [] {
+        const char *e = std::getenv("FQZ5_X32_GROUPS");
+        return e && e[0] == '0';
+    }();
+    return off ? UINT64_MAX : g_x32_min.load();
+}
+
 // The calling thread's helper contexts: their own streams and arenas, for
 // work the thread hands to helper threads to run beside its own
 // (fqz5_sections_try: LZP3, fqz and sequence-model candidates beside the
@@ -733,6 +742,8 @@ int fqz5_set_host_encode(int mode) {
     g_host_enc.store(mode < 0 || mode > 3 ? 2 : mode);
     return prev;
 }
+
+uint64_t fqz5_set_x32_group_min(uint64_t n) { return g_x32_min.exchange(n); }
 
 void fqz5_fqz_dec_counts(uint64_t *out2) {
     out2[0] = fqz_dec_blocks(false);

@@ -532,6 +532,10 @@ bool small_decoder_on();
 int host_decode_mode();
 // the encoder's bare rANS 4x16 chains on host cores (fqz5_set_host_encode)
 int host_encode_mode();
+// 32-state encoder jobs of this many symbols and more run as lane groups
+// (k_enc_chain_x32g; fqz5_set_x32_group_min); UINT64_MAX under
+// $FQZ5_X32_GROUPS=0: none do
+uint64_t x32_group_min();
 // quality blocks decoded by the general (false) / small (true) fqz decoder
 uint64_t fqz_dec_blocks(bool small);
 // fqz5_fqz_path_counts: blocks per fqz decoder variant (launch_group's var,

@@ -187,11 +187,16 @@ inline int dec_variant(const DecJob &J) {
 
 enum : int {
     EV_E2W_O0 = 0, EV_E2W_O1, EV_E1W_O1_COMPACT, EV_E32_O0, EV_E32_O1, EV_E32_O1_COMPACT,
+    EV_E32G_O0, EV_E32G_O1, EV_E32G_O1_COMPACT,    // k_enc_chain_x32g: lane groups
     EV_COUNT
 };
 constexpr const char *ENC_VARIANT_NAMES[EV_COUNT] = {
-    "E2W_O0", "E2W_O1", "E1W_O1_COMPACT", "E32_O0", "E32_O1", "E32_O1_COMPACT"};
+    "E2W_O0", "E2W_O1", "E1W_O1_COMPACT", "E32_O0", "E32_O1", "E32_O1_COMPACT",
+    "E32G_O0", "E32G_O1", "E32G_O1_COMPACT"};
 // (enc_variant: below, behind enc_chain_2w)
+// States per workgroup of k_enc_chain_x32g: a 32-state job runs as 32 / X32_LG
+// one-wave workgroups with the 4-state chunk geometry.
+constexpr int X32_LG = 4;
 
 // RLE encode of one leaf input; saved[] marks the RLE symbols.
 struct RleItem {
@@ -279,13 +284,17 @@ uint32_t enc_lds_bytes(int o1, uint32_t A);
 uint32_t enc_replay_lds_bytes(int o1, uint32_t A);
 bool enc_chain_2w(int o1, int nx, uint32_t A);       // runs k_enc_chain2w
 uint32_t enc_2w_lds_bytes(int o1, uint32_t A);
-inline int enc_variant(bool o1, int nx, uint32_t A) {
+// grouped: a 32-state job on k_enc_chain_x32g (rans_compress.cpp x32_grouped)
+inline int enc_variant(bool o1, int nx, uint32_t A, bool grouped = false) {
     if (enc_chain_2w(o1, nx, A)) return o1 ? EV_E2W_O1 : EV_E2W_O0;
     if (nx == 4) return EV_E1W_O1_COMPACT;       // (NX=4 off k_enc_chain2w: the table is compact)
-    if (!o1) return EV_E32_O0;
+    if (!o1) return grouped ? EV_E32G_O0 : EV_E32_O0;
+    if (grouped) return enc_tab_compact(true, A) ? EV_E32G_O1_COMPACT : EV_E32G_O1;
     return enc_tab_compact(true, A) ? EV_E32_O1_COMPACT : EV_E32_O1;
 }
 hipError_t launch_enc_chain2w(const EncJob *d_jobs, int njobs, uint32_t lds, hipStream_t s);
+// 32-state jobs only, 32 / X32_LG workgroups each; lds as launch_enc_chain
+hipError_t launch_enc_chain_x32g(const EncJob *d_jobs, int njobs, uint32_t lds, hipStream_t s);
 uint32_t dec_lds_bytes(uint32_t rows, int bits, int mode);
 hipError_t launch_enc_chain(const EncJob *d_jobs, int njobs, uint32_t lds, hipStream_t s);
 // d_items: uint32 pairs {job index, first chunk}

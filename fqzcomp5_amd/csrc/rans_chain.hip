@@ -117,9 +117,18 @@ static DEV uint32_t enc_steps(uint32_t n) {
     return O1 ? n - uint32_t(NX - 1) * (n / NX) : (n + NX - 1) / NX;
 }
 
-template <bool O1, int NX, bool TLDS>
-static DEV void chain_body(const EncJob &J) {
-    constexpr uint32_t S = enc_chunk<NX>();
+// One wave runs LG of the stream's NX chains, states z0 .. z0 + LG - 1.
+// LG == NX is the whole stream.  LG < NX (k_enc_chain_x32g) is a lane group
+// of a 32-state stream: the states are independent chains, only their words
+// interleave (k_enc_replay does that from the checkpoints), so a group
+// stages ENC_ENT / LG steps of its own states per chunk, shares nothing with
+// the other groups but the read-only input and table, and leaves its LG
+// words of every checkpoint, one each enc_chunk<NX>() steps.
+template <bool O1, int NX, bool TLDS, int LG = NX>
+static DEV void chain_body(const EncJob &J, uint32_t z0 = 0) {
+    static_assert(LG <= NX && NX % LG == 0, "a lane group divides the states");
+    constexpr uint32_t S = ENC_ENT / LG;           // steps per staged chunk
+    constexpr uint32_t CK = enc_chunk<NX>();       // steps per checkpoint
     constexpr int R = int(ENC_ENT / 64);           // entries staged per lane
     uint8_t *lds = reinterpret_cast<uint8_t *>(chain_lds);
     uint4 *ent = reinterpret_cast<uint4 *>(lds);
@@ -147,20 +156,25 @@ static DEV void chain_body(const EncJob &J) {
     const uint32_t jtop = (T - 1) / S;
     const auto in = buf(J.in, n);
 
-    // Staged entry r of lane l is i = l + 64r: O0 (step kk, lane z) with
-    // i = kk*NX + z; O1 chain-major, i = z*S + kk.  It lands at
-    // ent[(S-1-kk)*NX + z] so that the chain reads ascending addresses.
+    // Staged entry r of lane l is i = l + 64r: O0 (step kk, state z0 + zl)
+    // with i = kk*LG + zl; O1 chain-major, i = zl*S + kk.  It lands at
+    // ent[(S-1-kk)*LG + zl] so that the chain reads ascending addresses.
     uint32_t sb[R], cb[R];
+    // O0: the input offset of entry i of chunk j
+    auto o0_off = [&](uint32_t j, uint32_t i) {
+        if (LG == NX) return NX * S * j + i;
+        return uint32_t(NX) * (S * j + i / LG) + z0 + i % LG;
+    };
     auto issue = [&](uint32_t j) {
 #pragma unroll
         for (int r = 0; r < R; r++) {
             const uint32_t i = uint32_t(l) + 64u * r;
             if (O1) {
-                const uint32_t z = i / S, k = j * S + i % S;
+                const uint32_t z = z0 + i / S, k = j * S + i % S;
                 sb[r] = ld8(in, z * isz + k);
                 cb[r] = ld8(in, z * isz + k - 1u);
             } else {
-                sb[r] = ld8(in, NX * S * j + i);
+                sb[r] = ld8(in, o0_off(j, i));
             }
         }
     };
@@ -169,24 +183,24 @@ static DEV void chain_body(const EncJob &J) {
 #pragma unroll
         for (int r = 0; r < R; r++) {
             const uint32_t i = uint32_t(l) + 64u * r;
-            uint32_t z, kk, idx;
+            uint32_t zl, kk, idx;
             bool ok;
             if (O1) {
-                z = i / S;
+                zl = i / S;
                 kk = i % S;
                 const uint32_t k = j * S + kk;
-                ok = k < ((z == NX - 1) ? T : isz);
+                ok = k < ((z0 + zl == NX - 1) ? T : isz);
                 const uint32_t ctx = k ? cb[r] : 0u;
                 idx = uint32_t(rm[ctx]) * A + rm[sb[r]];
             } else {
-                z = i % NX;
-                kk = i / NX;
-                ok = NX * S * j + i < n;
+                zl = i % LG;
+                kk = i / LG;
+                ok = o0_off(j, i) < n;
                 idx = sb[r];
             }
             uint4 e = TLDS ? tab[ok ? idx : 0u] : enc_expand(ctab[ok ? idx : 0u], J.bits, rc);
             if (!ok) e = ID;
-            ent[(S - 1 - kk) * NX + z] = e;
+            ent[(S - 1 - kk) * LG + zl] = e;
         }
     };
 
@@ -194,11 +208,12 @@ static DEV void chain_body(const EncJob &J) {
     __syncthreads();
     stage(jtop);
 
-    const int zl = l & (NX - 1);
-    const bool writer = l < NX;
+    const int zl = l & (LG - 1);
+    const bool writer = l < LG;
     uint32_t x = RANS_LOW_D;
-    uint32_t *ck = J.ck + zl;
+    uint32_t *ck = J.ck + z0 + zl;
     const uint4 *ep = ent + zl;
+    const uint32_t cktop = (T - 1) / CK;              // (LG < NX) the first checkpoint's chunk
 
     auto step = [&](const uint4 e) {
         const bool c = x > e.y;
@@ -215,8 +230,10 @@ static DEV void chain_body(const EncJob &J) {
 #ifdef FQZ5_CHAIN_PROBE
         const uint64_t tp0 = __builtin_amdgcn_s_memtime();
 #endif
-        if (writer) *ck = x;
-        ck += NX;
+        if (LG == NX) {
+            if (writer) *ck = x;
+            ck += NX;
+        }
         if (j > 0) issue(uint32_t(j - 1));
         // ---- the chain: entries of block b+1 are read while block b runs
         // (at most 16 reads in flight, within what lgkmcnt can track);
@@ -226,16 +243,28 @@ static DEV void chain_body(const EncJob &J) {
         // only waits for block b's own reads, issued a block earlier.  (All
         // 64 lanes run it: limiting exec to the NX state lanes measured
         // slower here, unlike the decoder.)
+        // A lane group checkpoints inside its staged chunk, before every CK
+        // steps from the stream's top chunk on: the steps above it are past
+        // every state's input and no checkpoint exists for them.
         constexpr int CB = 8;
         uint4 E[2][CB];
 #pragma unroll
-        for (int i = 0; i < CB; i++) E[0][i] = ep[i * NX];
+        for (int i = 0; i < CB; i++) E[0][i] = ep[i * LG];
 #pragma unroll
         for (uint32_t b = 0; b < S / CB; b++) {
+            if (LG < NX && b % (CK / CB) == 0) {
+                const uint32_t jc = uint32_t(j) * (S / CK) + (S / CK - 1 - b / (CK / CB));
+                if (jc <= cktop) {
+                    // (a global store: a flat one would count against the
+                    // chain's LDS reads)
+                    if (writer) *(__attribute__((address_space(1))) uint32_t *)(ck) = x;
+                    ck += NX;
+                }
+            }
             step(E[b & 1][0]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int i = 0; i < CB; i++) E[(b + 1) & 1][i] = ep[(CB * (b + 1) + i) * NX];
+            for (int i = 0; i < CB; i++) E[(b + 1) & 1][i] = ep[(CB * (b + 1) + i) * LG];
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int i = 1; i < CB; i++) step(E[b & 1][i]);
@@ -403,6 +432,20 @@ __global__ __launch_bounds__(64) void k_enc_chain(const EncJob *jobs) {
     } else {
         if (J.nx == 32) chain_body<false, 32, true>(J);
         else            chain_body<false, 4, true>(J);
+    }
+}
+
+// One 32-state stream as 32 / X32_LG workgroups of one wave, each chaining
+// X32_LG consecutive states: blockIdx.x the group, blockIdx.y the job.  No
+// group waits for another.
+__global__ __launch_bounds__(64) void k_enc_chain_x32g(const EncJob *jobs) {
+    const EncJob J = jobs[blockIdx.y];
+    const uint32_t z0 = blockIdx.x * uint32_t(X32_LG);
+    if (J.remap != nullptr) {
+        if (!enc_tab_compact(true, uint32_t(J.A))) chain_body<true, 32, true, X32_LG>(J, z0);
+        else                                       chain_body<true, 32, false, X32_LG>(J, z0);
+    } else {
+        chain_body<false, 32, true, X32_LG>(J, z0);
     }
 }
 
@@ -1467,6 +1510,14 @@ hipError_t launch_enc_chain(const EncJob *d_jobs, int njobs, uint32_t lds, hipSt
     static bool attr = false;
     if (!attr) { lds_attr(reinterpret_cast<const void *>(k_enc_chain)); attr = true; }
     hipLaunchKernelGGL(k_enc_chain, dim3(njobs), dim3(64), lds, s, d_jobs);
+    return hipGetLastError();
+}
+
+hipError_t launch_enc_chain_x32g(const EncJob *d_jobs, int njobs, uint32_t lds, hipStream_t s) {
+    if (!njobs) return hipSuccess;
+    static bool attr = false;
+    if (!attr) { lds_attr(reinterpret_cast<const void *>(k_enc_chain_x32g)); attr = true; }
+    hipLaunchKernelGGL(k_enc_chain_x32g, dim3(32 / X32_LG, njobs), dim3(64), lds, s, d_jobs);
     return hipGetLastError();
 }
 

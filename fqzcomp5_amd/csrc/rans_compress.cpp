@@ -722,11 +722,12 @@ void Compressor::stage_encode() {
     // Chain pass: two launches on two queues, jobs whose tables fit a small
     // LDS footprint (many waves per CU) and the rest.  Then the replay
     // passes over all chunks of all jobs (rans_chain.hip).
-    std::vector<EncJob> ejs, ejb, eall;
+    std::vector<EncJob> ejs, ejb, ejg, eall;
     int long_s = -1, long_b = -1;            // the longest chain of ejs / ejb
+    const uint64_t group_min = x32_group_min();
     std::vector<uint32_t *> ck_of(jobs_.size(), nullptr);
     std::vector<uint32_t> items;
-    uint32_t lds_s = 0, lds_b = 0, lds_r = 0;
+    uint32_t lds_s = 0, lds_b = 0, lds_g = 0, lds_r = 0;
     std::vector<int> order;
     for (size_t i = 0; i < jobs_.size(); i++)
         if (jobs_[i].n) order.push_back(int(i));
@@ -890,20 +891,25 @@ void Compressor::stage_encode() {
         const EncJob e{j.d_in, d_tab, d_remap, j.d_end, d_lens + i, d_ck, d_cnt,
                        j.n, j.nx, j.bits, j.A, nch};
         // ejs: two-wave chains (NX=4, table in LDS: the long ones);
-        // ejb: the rest (X32, O1 tables too big for LDS)
+        // ejg: long X32 chains, as lane groups (k_enc_chain_x32g);
+        // ejb: the rest (short X32, O1 tables too big for LDS)
+        const bool grouped = !on_host[i] && j.nx == 32 && j.n >= group_min;
         if (on_host[i]) {
             // (its checkpoints come from a host core, below)
         } else if (enc_chain_2w(j.o1, j.nx, uint32_t(j.A))) {
             if (ejs.empty()) long_s = i;
             ejs.push_back(e);
             lds_s = std::max(lds_s, enc_2w_lds_bytes(j.o1, uint32_t(j.A)));
+        } else if (grouped) {
+            ejg.push_back(e);
+            lds_g = std::max(lds_g, enc_lds_bytes(j.o1, uint32_t(j.A)));
         } else {
             if (ejb.empty()) long_b = i;
             ejb.push_back(e);
             lds_b = std::max(lds_b, enc_lds_bytes(j.o1, uint32_t(j.A)));
         }
         if (!on_host[i])
-            g_enc_variant[enc_variant(j.o1, j.nx, uint32_t(j.A))].fetch_add(1, std::memory_order_relaxed);
+            g_enc_variant[enc_variant(j.o1, j.nx, uint32_t(j.A), grouped)].fetch_add(1, std::memory_order_relaxed);
         const uint32_t per = enc_replay_chunks(j.nx);
         for (uint32_t c0 = 0; c0 < nch; c0 += per) {
             items.push_back(uint32_t(eall.size()));
@@ -913,8 +919,10 @@ void Compressor::stage_encode() {
         lds_r = std::max(lds_r, enc_replay_lds_bytes(j.o1, uint32_t(j.A)));
     }
     EventPair ev(g_.prof.on && !order.empty(), g_.stream);
-    lds_s = g_.chain_lds(lds_s, ejs.size() + ejb.size());
-    lds_b = g_.chain_lds(lds_b, ejs.size() + ejb.size());
+    const size_t nwg = ejs.size() + ejb.size() + ejg.size() * size_t(32 / X32_LG);
+    lds_s = g_.chain_lds(lds_s, nwg);
+    lds_b = g_.chain_lds(lds_b, nwg);
+    lds_g = g_.chain_lds(lds_g, nwg);
     // per-kernel spans (fqz5_profile_read_all): their bytes once the
     // output lengths are known, below
     long tk_2w = -1, tk_1w = -1, tk_r0 = -1, tk_r1 = -1;
@@ -926,10 +934,21 @@ void Compressor::stage_encode() {
     hipEvent_t ts[2] = {nullptr, nullptr}, tl[2] = {nullptr, nullptr};
     if (timed(long_s)) { ts[0] = hc.event(hipEventDefault); ts[1] = hc.event(hipEventDefault); }
     if (timed(long_b)) { tl[0] = hc.event(hipEventDefault); tl[1] = hc.event(hipEventDefault); }
+    // the one-wave chains: the lane groups of the long X32 jobs, then the
+    // rest, under one span
+    auto launch_1w = [&]() {
+        const EncJob *dg = ejg.empty() ? nullptr : g_.upload(ejg);
+        const EncJob *db = ejb.empty() ? nullptr : g_.upload(ejb);
+        ProfSpan sp(PK_ENC_CHAIN, g_.stream);
+        FQZ5_HIP(launch_enc_chain_x32g(dg, int(ejg.size()), lds_g, g_.stream));
+        if (tl[0]) FQZ5_HIP(hipEventRecord(tl[0], g_.stream));
+        FQZ5_HIP(launch_enc_chain(db, int(ejb.size()), lds_b, g_.stream));
+        if (tl[1]) FQZ5_HIP(hipEventRecord(tl[1], g_.stream));
+        tk_1w = sp.end(0);
+    };
     const double t_launch = now_ms();
     if (!ejs.empty()) {
         const EncJob *d = g_.upload(ejs);
-        const EncJob *db = ejb.empty() ? nullptr : g_.upload(ejb);
         g_.fork();
         {
             ProfSpan sp(PK_ENC_CHAIN2W, g_.stream2);
@@ -938,23 +957,12 @@ void Compressor::stage_encode() {
             if (ts[1]) FQZ5_HIP(hipEventRecord(ts[1], g_.stream2));
             tk_2w = sp.end(0);
         }
-        if (db) {
-            ProfSpan sp(PK_ENC_CHAIN, g_.stream);
-            if (tl[0]) FQZ5_HIP(hipEventRecord(tl[0], g_.stream));
-            FQZ5_HIP(launch_enc_chain(db, int(ejb.size()), lds_b, g_.stream));
-            if (tl[1]) FQZ5_HIP(hipEventRecord(tl[1], g_.stream));
-            tk_1w = sp.end(0);
-        }
+        if (!ejb.empty() || !ejg.empty()) launch_1w();
         g_.join();
-    } else if (!ejb.empty()) {
-        const EncJob *db = g_.upload(ejb);
-        ProfSpan sp(PK_ENC_CHAIN, g_.stream);
-        if (tl[0]) FQZ5_HIP(hipEventRecord(tl[0], g_.stream));
-        FQZ5_HIP(launch_enc_chain(db, int(ejb.size()), lds_b, g_.stream));
-        if (tl[1]) FQZ5_HIP(hipEventRecord(tl[1], g_.stream));
-        tk_1w = sp.end(0);
+    } else if (!ejb.empty() || !ejg.empty()) {
+        launch_1w();
     }
-    g_enc_gpu += ejs.size() + ejb.size();
+    g_enc_gpu += ejs.size() + ejb.size() + ejg.size();
     g_enc_host += hc.chains.size();
     // the host chains' checkpoints into their jobs' EncJob::ck, behind the
     // GPU-placed chains in stream order and before the replay passes
@@ -1035,7 +1043,7 @@ void Compressor::stage_encode() {
             std::fprintf(stderr, "; host chains %zu of %zu (longest %.1f ms, joined %.1f ms after the launch, "
                          "chains waited for input copies that landed %.1f .. %.1f ms after the first was issued), ns per symbol "
                          "o0 host %.2f gpu %.2f, o1 host %.2f gpu %.2f",
-                         hc.chains.size(), hc.chains.size() + ejs.size() + ejb.size(), host_longest, host_joined,
+                         hc.chains.size(), hc.chains.size() + ejs.size() + ejb.size() + ejg.size(), host_longest, host_joined,
                          first_landed > 0 ? first_landed - t_copy0 : 0.0, last_landed > 0 ? last_landed - t_copy0 : 0.0,
                          host::chain_ns(host::CK_RANS_ENC_O0, false), host::chain_ns(host::CK_RANS_ENC_O0, true),
                          host::chain_ns(host::CK_RANS_ENC_O1, false), host::chain_ns(host::CK_RANS_ENC_O1, true));

@@ -317,6 +317,15 @@ def set_host_encode(mode: int) -> int:
     return int(so.fqz5_set_host_encode(mode))
 
 
+def set_x32_group_min(n: int) -> int:
+    """fqz5_set_x32_group_min: 32-state encoder chains of n symbols and more
+    run as lane groups (k_enc_chain_x32g); the previous threshold."""
+    so = load()
+    so.fqz5_set_x32_group_min.restype = C.c_uint64
+    so.fqz5_set_x32_group_min.argtypes = [C.c_uint64]
+    return int(so.fqz5_set_x32_group_min(n))
+
+
 def rans_enc_chain_counts() -> tuple[int, int]:
     """Encoder chains placed so far: (on host cores, on the GPU)."""
     c = (C.c_uint64 * 2)()

@@ -207,6 +207,13 @@ int fqz5_unlzp_host(const unsigned char *in, size_t in_len, unsigned char *out, 
  * the setting.  32-state (X32) chains always run on the GPU.  Returns the
  * previous setting. */
 int fqz5_set_host_encode(int mode);
+/* 32-state (X32) encoder chains of n symbols and more run as lane groups:
+ * k_enc_chain_x32g, eight one-wave workgroups of four states each, which
+ * leave the checkpoints k_enc_chain would have left, so the output bytes do
+ * not depend on the setting.  Shorter ones run on k_enc_chain.  The default
+ * is 2^20; 0 groups every 32-state chain.  $FQZ5_X32_GROUPS=0 keeps all of
+ * them on k_enc_chain whatever is set here.  Returns the previous setting. */
+uint64_t fqz5_set_x32_group_min(uint64_t n);
 /* Encoder chains placed so far: out2[0] on host cores, out2[1] on the GPU. */
 void fqz5_rans_enc_chain_counts(uint64_t *out2);
 /* GPU-launched rANS chain jobs so far, by the kernel body that ran them: the
